@@ -1,7 +1,14 @@
 """WAM attribution throughput bench on MI355X (the BASELINE.json metric and its five configs).
 
-    python bench.py [--config c2] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config c2] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps (--steps is the number of timed explainer calls)
+and prints the result line: metric, value, ms_per_step and the roofline of the dominant WAM kernel
+as the timed steps' own HIP events give it. --dump-outputs DIR then writes what the last timed
+step returned as DIR/<name>.npy (see dump_outputs). Everything that takes runs of its own -- the
+PMC traffic passes, the CPU baseline, parity, variants, ceilings, the host-copy timings, the
+collectives' and weak-scaling timings at N > 1 -- is behind --full.
 
 Workloads (BASELINE.json `configs`; synthetic data, random-init weights -- no
 network). One STEP = one explainer call on the config's whole batch:
@@ -23,10 +30,10 @@ dist=True -- c2 over the batch (each rank a contiguous image range, the per-samp
 maxima combined by an all-reduce MAX, the rows gathered), c4 over the IG path steps as BASELINE
 configs[3] names it (trapezoid partials summed by one fp32 all-reduce), c3/c5 over the noise
 samples (partial accumulators summed by an all-reduce) -- so "scaling" is "strong" and value =
-the call's attributions / max-over-ranks time. N > 1 also reports the collectives' time and a
-weak-scaling figure (each rank its own batch, no collective) as secondary fields.
+the call's attributions / max-over-ranks time. With --full, N > 1 also reports the collectives'
+time and a weak-scaling figure (each rank its own batch, no collective) as secondary fields.
 
-The JSON line also carries
+The JSON line also carries (traffic, cpu_baseline and the extras with --full only)
   roofline      the dominant WAM kernel (largest total time), timed live with HIP events that
                 libwam_hip.so records on the launch stream: SURVEY 8(d) algorithmic bytes per
                 launch / mean launch time vs the 8 TB/s HBM peak; traffic = HBM bytes per launch
@@ -177,6 +184,14 @@ def parse(argv=None):
                     help="2D: fp32 model hand-off (cast / layout passes) instead of bf16 NHWC (A/B)")
     ap.add_argument("--no-optimize-model", action="store_true",
                     help="run the model as is under autocast instead of the BN-folded copy (model_opt.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (at most 64 MB in "
+                         "all; a fixed, seeded sample of a larger output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: PMC traffic passes, the CPU "
+                         "baseline, parity / variants / ceilings, host-copy timings, and at N > 1 the "
+                         "collectives' and weak-scaling timings (--pmc / --cpu-baseline / --extras choose "
+                         "among them)")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"])
@@ -836,11 +851,126 @@ def rank_slice(args, wl):
     return 0
 
 
+# ============================================================================ --dump-outputs
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # array payload; leaves room for the .npy headers under 64 MB
+DUMP_SEED = 20240229
+
+
+def _output_arrays(out):
+    """(name, float32 / float64 ndarray) for every array a caller of the timed call receives."""
+    if isinstance(out, dict):
+        items = [(str(k), v) for k, v in out.items()]
+    elif isinstance(out, (tuple, list)):
+        items = [("out%d" % i, v) for i, v in enumerate(out)]
+    else:
+        items = [("out0", out)]
+    arrays = []
+    for name, v in items:
+        if isinstance(v, (tuple, list)) and not all(np.isscalar(e) for e in v):  # e.g. per-level coefficient maps
+            arrays += [("%s_%d" % (name, j), a) for j, (_, a) in enumerate(sum((_output_arrays(e) for e in v), []))]
+            continue
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        arrays.append((name, a))
+    return arrays
+
+
+def dump_outputs(out, outdir):
+    """Write what the last timed step returned as outdir/<name>.npy (out0, out1, ... in the order of
+    the call's return value; float32 / float64 as returned). Within DUMP_BUDGET_BYTES in all every
+    array is written whole; beyond it each array keeps the same fraction of its elements, a sorted
+    sample of flat indices drawn from a fixed seed (the same indices for the same shapes), so the
+    files of two builds line up element for element. index.json names the files, the full shapes
+    and whether a file is such a sample."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = _output_arrays(out)
+    total = sum(a.nbytes for _, a in arrays)
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    index = {}
+    for k, (name, a) in enumerate(arrays):
+        sampled = frac < 1.0 and a.size > 1
+        if sampled:
+            keep = max(1, int(a.size * frac))
+            idx = np.sort(np.random.RandomState(DUMP_SEED + k).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+        index[name] = {"file": name + ".npy", "dtype": str(a.dtype), "saved_shape": list(a.shape),
+                       "full_shape": list(arrays[k][1].shape), "sampled": bool(sampled),
+                       "sample": "np.sort(np.random.RandomState(%d).choice(size, %d, replace=False)) of the flat "
+                                 "array" % (DUMP_SEED + k, a.size) if sampled else None}
+    with open(os.path.join(outdir, "index.json"), "w") as f:
+        json.dump(index, f, indent=1)
+
+
+# ============================================================================ --full: secondary timings
+def secondary_timings(wl, dev, args, ex, x, xd, y, dt, n_local, world, axis):
+    """--full: what a call costs beside its timed steps (host copies, cold noise cache), and at
+    N > 1 the collectives' and weak-scaling timings; secondary fields of the line."""
+    from wam_amd import engine
+    secondary = {}
+    # the drop-in caller hands the explainer a host tensor (lib/wam_2D.py:392,114); the class moves
+    # it once per call. The timed steps start from an HBM-resident x; the host -> device copy of the
+    # same (pageable) tensor is timed here and reported beside the value, never folded into it.
+    h2d = []
+    for _ in range(5):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        x.to(dev)
+        torch.cuda.synchronize(dev)
+        h2d.append(time.perf_counter() - t0)
+    h2d_s = sorted(h2d)[2]
+    secondary["h2d_input"] = {
+        "ms": round(h2d_s * 1e3, 3), "bytes": int(x.numel() * x.element_size()),
+        "GB_per_s": round(x.numel() * x.element_size() / h2d_s / 1e9, 2),
+        "value_including_h2d": round(n_local / (dt / args.steps + h2d_s), 3),
+        "what": "median of 5 host->device copies of the call's (pageable) input, as the drop-in caller passes it; "
+                "value_including_h2d = this rank's items / (ms_per_step + that copy)"}
+    if wl.kw.get("noise", "numpy") == "numpy" and wl.kw.get("method") == "smooth":
+        # parity-mode noise: the legacy numpy stream is drawn on the host once per (seed, shape,
+        # batch) and replayed from the device afterwards (engine.LegacyNoise); a first ("cold")
+        # call pays the host generation
+        engine.clear_noise_cache()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        ex(xd, y)
+        torch.cuda.synchronize(dev)
+        secondary["noise_cache"] = {
+            "cold_call_ms": round((time.perf_counter() - t0) * 1e3, 2), "warm_call_ms": round(dt / args.steps * 1e3, 2),
+            "what": "timed calls replay the reference's legacy numpy noise stream from the device (drawn once per "
+                    "seed / shape / batch, scaled per call, bit-exact); cold_call_ms = one call after clearing it"}
+    if wl.dim == 2:
+        log(".scales host copy")
+        # .scales (lib/wam_2D.py:413,457): the reprojection kernel runs inside every timed call;
+        # its float64 host copy is made on first access -- its cost, outside the timed region:
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        sc = ex.scales
+        secondary["scales_host_copy"] = {
+            "ms": round((time.perf_counter() - t0) * 1e3, 2), "bytes": int(sc.nbytes),
+            "what": ".scales reprojection (k_reproject) runs in every timed call on the device; this is the one-off "
+                    "device -> host float64 copy on first access of ex.scales, not in the timed region"}
+        del sc
+    if world > 1:
+        log("collectives timing")
+        secondary["collectives"] = collectives_timing(wl, dev, world, axis)
+    if world > 1 and args.extras == "auto":
+        log("weak scaling: each rank its own %d-item batch" % wl.n)
+        exw = build_explainer(wl, dev, args, dist_on=False)  # each rank its own batch, no collective
+        dtw, _, _ = timed(lambda: exw(xd, y), 2, 1, world, dev)
+        secondary["weak_scaling"] = {"value": round(wl.n * 2 * world / dtw, 3), "ms_per_step": round(dtw / 2 * 1e3, 2),
+                                     "what": "each rank explains its own %d-item batch (no collective), 2 steps"
+                                             % wl.n}
+    return secondary
+
+
 # ============================================================================ main
 def main():
     args = parse()
     if args.wam_probe:
         return wam_probe(args)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.pmc = args.cpu_baseline = args.extras = "off"
     heartbeat()
     if args.rank_slice:
         return rank_slice(args, workload(args.config))
@@ -904,59 +1034,12 @@ def main():
         roof["traffic_error"] = traffic["error"]
 
     log("timed: %.1f ms per step" % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        log("outputs of the last timed step -> %s" % args.dump_outputs)
+        dump_outputs(out, args.dump_outputs)
     secondary = {}
-    # the drop-in caller hands the explainer a host tensor (lib/wam_2D.py:392,114); the class moves
-    # it once per call. The timed steps start from an HBM-resident x; the host -> device copy of the
-    # same (pageable) tensor is timed here and reported beside the value, never folded into it.
-    h2d = []
-    for _ in range(5):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        x.to(dev)
-        torch.cuda.synchronize(dev)
-        h2d.append(time.perf_counter() - t0)
-    h2d_s = sorted(h2d)[2]
-    secondary["h2d_input"] = {
-        "ms": round(h2d_s * 1e3, 3), "bytes": int(x.numel() * x.element_size()),
-        "GB_per_s": round(x.numel() * x.element_size() / h2d_s / 1e9, 2),
-        "value_including_h2d": round(n_local / (dt / args.steps + h2d_s), 3),
-        "what": "median of 5 host->device copies of the call's (pageable) input, as the drop-in caller passes it; "
-                "value_including_h2d = this rank's items / (ms_per_step + that copy)"}
-    if wl.kw.get("noise", "numpy") == "numpy" and wl.kw.get("method") == "smooth":
-        # parity-mode noise: the legacy numpy stream is drawn on the host once per (seed, shape,
-        # batch) and replayed from the device afterwards (engine.LegacyNoise); a first ("cold")
-        # call pays the host generation
-        engine.clear_noise_cache()
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        ex(xd, y)
-        torch.cuda.synchronize(dev)
-        secondary["noise_cache"] = {
-            "cold_call_ms": round((time.perf_counter() - t0) * 1e3, 2), "warm_call_ms": round(dt / args.steps * 1e3, 2),
-            "what": "timed calls replay the reference's legacy numpy noise stream from the device (drawn once per "
-                    "seed / shape / batch, scaled per call, bit-exact); cold_call_ms = one call after clearing it"}
-    if wl.dim == 2:
-        log(".scales host copy")
-        # .scales (lib/wam_2D.py:413,457): the reprojection kernel runs inside every timed call;
-        # its float64 host copy is made on first access -- its cost, outside the timed region:
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        sc = ex.scales
-        secondary["scales_host_copy"] = {
-            "ms": round((time.perf_counter() - t0) * 1e3, 2), "bytes": int(sc.nbytes),
-            "what": ".scales reprojection (k_reproject) runs in every timed call on the device; this is the one-off "
-                    "device -> host float64 copy on first access of ex.scales, not in the timed region"}
-        del sc
-    if world > 1:
-        log("collectives timing")
-        secondary["collectives"] = collectives_timing(wl, dev, world, axis)
-    if world > 1 and args.extras == "auto":
-        log("weak scaling: each rank its own %d-item batch" % wl.n)
-        exw = build_explainer(wl, dev, args, dist_on=False)  # each rank its own batch, no collective
-        dtw, _, _ = timed(lambda: exw(xd, y), 2, 1, world, dev)
-        secondary["weak_scaling"] = {"value": round(wl.n * 2 * world / dtw, 3), "ms_per_step": round(dtw / 2 * 1e3, 2),
-                                     "what": "each rank explains its own %d-item batch (no collective), 2 steps"
-                                             % wl.n}
+    if args.full:
+        secondary = secondary_timings(wl, dev, args, ex, x, xd, y, dt, n_local, world, axis)
 
     cpu, cpu_ref = None, None
     if rank == 0 and world == 1 and args.cpu_baseline == "auto":

@@ -267,7 +267,9 @@ int wam_trapz_f32(int64_t groups, int64_t k0, int64_t len, const float* src, con
 
 /* .scales side output (lib/wam_2D.py:488-536 reproject_wam): for each item and level j,
  * out[item, j] = sum over the H, V, D quadrants of bilinear (cv2 INTER_LINEAR, half-pixel)
- * upsampling to size x size; with approx, out[item, J] = upsampled approximation corner. */
+ * upsampling to size x size; with approx, out[item, J] = upsampled approximation corner. The
+ * quadrants split at int(size / 2^j); WAM_ERR_INVALID_ARG when size < 2^levels (an empty
+ * quadrant: the reference's resize raises on it). */
 int wam_reproject_scales(int64_t items, int size, int levels, int approx, const double* avg,
                          double* out, void* stream);
 

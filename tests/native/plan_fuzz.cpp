@@ -106,6 +106,15 @@ int main() {
   CHECK(wam_item_sigma_ws_bytes(0, 5) == 0);
   CHECK(wam_item_sigma_ws_bytes(64, 150528) > 0);
   CHECK(wam_item_sigma_ws_bytes(1, int64_t(1) << 40) > 0);
+  // .scales of a map smaller than 2^levels: an empty coarsest quadrant, refused before any launch
+  // (the pointers are never used)
+  {
+    double avg[36] = {0}, out[4 * 36] = {0};
+    const int small[3][2] = {{4, 3}, {6, 3}, {3, 2}};
+    for (const auto& c : small)
+      for (int approx = 0; approx <= 1; ++approx)
+        CHECK(wam_reproject_scales(1, c[0], c[1], approx, avg, out, nullptr) == WAM_ERR_INVALID_ARG);
+  }
   std::printf("plan_fuzz: %d random plans probed, %d plans created, %d with fused-kernel caps, %d failed checks\n",
               n, made, with_caps, fails);
   return fails ? 1 : 0;

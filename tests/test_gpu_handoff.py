@@ -137,3 +137,59 @@ def test_handoff_end_to_end_matches_fp32_handoff():
     # side attributes of the last pass from the bf16 gradient (widened on access)
     gc = ex.wam.gradient_coeffs
     assert len(gc) == 4 and gc[0].shape[:2] == (4, 3)
+
+
+@pytest.mark.parametrize("int_label", [False, True])
+@pytest.mark.parametrize("N", [3, 5])
+def test_handoff_fp32_fallback_end_to_end(N, int_label):
+    """Previously unreached branch 8: the fp32 fallback of the bf16 hand-off (wam_2D.py
+    _handoff_groups, the only end-to-end hand-off test used 4 images): a batch whose size is
+    not a power of two has a loss scale 1 / N that is applied in fp32, so the model hands back an
+    fp32 planar gradient and the maps come from the fp32 kernel -- the default path
+    (bf16_handoff=True) of every such batch. Model and settings of
+    test_handoff_end_to_end_matches_fp32_handoff with 3 and 5 images, a list y and an int y, against
+    bf16_handoff=False at the same 2e-2 rel-L2 bar; gradient_coeffs and the recorded last gradient
+    keep the batch dimension N; the timing records show k_plane_maps and no k_plane_maps<bf16...>."""
+    import torch.nn as nn
+    from wam_amd import plan as P
+    from wam_amd.wam_2D import WaveletAttribution2D
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv = nn.Conv2d(3, 8, 3, padding=1)
+            self.bn = nn.BatchNorm2d(8)
+            self.fc = nn.Linear(8 * 16, 5)
+
+        def forward(self, x):
+            h = torch.tanh(self.bn(self.conv(x)))
+            return self.fc(torch.flatten(nn.functional.adaptive_avg_pool2d(h, 4), 1))
+
+    torch.manual_seed(0)
+    m = Net().eval().cuda()
+    x = torch.tensor(np.random.RandomState(1).standard_normal((N, 3, 64, 64)).astype(np.float32))
+    y = 2 if int_label else [1, 3, 0, 2, 4][:N]
+    kw = dict(wavelet="db4", J=3, method="smooth", n_samples=6, noise="philox", frame="native", sample_batch=4,
+              optimize_model=True, autocast_dtype=torch.bfloat16, channels_last=True)
+    P.timing_drain()
+    P.timing_enable(True)
+    ex = WaveletAttribution2D(m, **kw)
+    assert ex.bf16_handoff
+    a = ex(x, y)
+    torch.cuda.synchronize()
+    P.timing_enable(False)
+    names = {r[0] for r in P.timing_drain()}
+    assert "k_plane_maps" in names, names
+    assert not any(k.startswith("k_plane_maps<bf16") for k in names), names
+    assert "k_plane_syn<bf16nhwc>" in names, names  # the hand-off path itself ran (bf16 NHWC model input)
+    b = WaveletAttribution2D(m, bf16_handoff=False, **kw)(x, y)
+    assert a.shape == b.shape == (N, 64, 64)
+    rel = np.linalg.norm(a - b) / np.linalg.norm(b)
+    print("[handoff] N=%d int_label=%d rel-L2 = %.3g" % (N, int_label, rel))
+    assert rel <= 2e-2, rel
+    plan, _, _, n, c, last_g = ex.wam._pass
+    assert (n, c) == (N, 3) and last_g.dtype == torch.float32
+    assert ex.wam._planes(plan, last_g, n, c).shape == (N * 3,) + tuple(plan.rec_shape)
+    gc = ex.wam.gradient_coeffs
+    assert len(gc) == 4 and gc[0].shape[:2] == (N, 3)
+    assert all(t.shape[:2] == (N, 3) for lv in gc[1:] for t in lv)

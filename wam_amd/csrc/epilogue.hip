@@ -1047,6 +1047,9 @@ int wam_reproject_scales(int64_t items, int size, int levels, int approx, const 
                          void* stream) {
   if (items < 0 || size < 1 || levels < 1 || !avg || !out) return WAM_ERR_INVALID_ARG;
   if (levels > WAM_MAX_LEVELS) return WAM_ERR_UNSUPPORTED;
+  // size < 2^levels: the coarsest split int(size / 2^levels) is 0, an empty quadrant the reference's
+  // resize raises on (and lin_axis would clamp its tap to -1)
+  if ((size >> levels) == 0) return WAM_ERR_INVALID_ARG;
   int64_t work = items * (levels + (approx ? 1 : 0)) * (int64_t)size * size;
   if (work == 0) return WAM_OK;
   ReprojGeom g{};

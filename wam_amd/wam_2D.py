@@ -338,6 +338,10 @@ class WaveletAttribution2D(BaseWAM2D):
         if self._scales is None and self._scales_res is not None:
             self._scales = self._scales_host(self._scales_res, self.J, self.approx_coeffs)
         elif self._scales is None and self._avg_dev is not None:
+            if self._avg_dev.shape[1] == self._avg_dev.shape[2] and self._avg_dev.shape[1] >> self.J == 0:
+                # the reference raises when it builds them (cv2.resize of an empty quadrant)
+                raise ValueError("scales: a %d x %d map has no level-%d quadrants"
+                                 % (self._avg_dev.shape[1], self._avg_dev.shape[2], self.J))
             self._scales = self._reproject_dev(self._avg_dev, self.J, self.approx_coeffs)
         return self._scales
 
@@ -349,7 +353,9 @@ class WaveletAttribution2D(BaseWAM2D):
         self._avg_dev = avg_dev
         self._scales = None
         self._scales_res = None
-        if avg_dev.shape[1] == avg_dev.shape[2]:
+        # a map smaller than 2^J has an empty coarsest quadrant: no scales (the getter raises, as the
+        # reference does when it builds them); the attribution itself is returned as before
+        if avg_dev.shape[1] == avg_dev.shape[2] and avg_dev.shape[1] >> self.J > 0:
             self._scales_res = reproject_scales(avg_dev.contiguous(), self.J, self.approx_coeffs)
 
     # ------------------------------------------------------------------ estimators

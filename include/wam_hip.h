@@ -333,6 +333,48 @@ int wam_upsample_masks(int64_t n_masks, int64_t grid_len, const float* grid, int
 int wam_masked_sums(int64_t n_masks, int64_t len, const double* wam, int64_t grid_len, const float* grid,
                     const int32_t* cell, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Audio insertion / deletion / faithfulness of spectra / input fidelity (Eval1DWAM,
+ * src/evaluators.py:39-306). The reference's per-clip CPU loop (masks on the host, coeff * mask per
+ * band, float64 pywt.waverec of n_iter + 1 sets, numpy wf / wf.max()) becomes: wam_wavedec (mode
+ * reflect) once per group of clips, wam_rank_mask_coeffs, one wam_waverec, wam_peak_normalize, the
+ * mel front-end. The masks themselves are never stored.
+ * The selection rule shared by the two rank-mask entries, for mask m = 0 .. n_iter of a set whose
+ * ranking has rank_len slots: thr(0) = 0; thr(m) = min(m * n_comp, rank_len) for 0 < m < n_iter;
+ * thr(n_iter) = rank_len. A value whose mask slot is p is kept by mask m when
+ * (rank[s, p] < thr(m)) != (deletion != 0). A kept value is multiplied by 1.0f, a dropped one by
+ * 0.0f (so a dropped negative value is -0.0f and a dropped NaN stays NaN).
+ * ---------------------------------------------------------------------------------------------- */
+/* Ranking to masked coefficients. plan: a 1D plan (WAM_ERR_UNSUPPORTED otherwise) with K =
+ * wam_plan_coeff_numel values per item. coeffs: band-major coefficients of `sets` items, as
+ * wam_wavedec writes them (band b of item s starts at sets * off[b] + s * n_b, off[b] =
+ * wam_plan_band_offset, n_b the band length). rank [sets, rank_len] int32 (device): rank[s, p] = the
+ * position of mask slot p of set s in the descending importance order. pos [K] int32 (device), shared
+ * by all sets: pos[k] = the mask slot of the coefficient at per-item offset k (k = off[b] + e for
+ * element e of band b), in [0, rank_len), or -1 for the reference's pad column; any other value is
+ * read as -1. A pad-column coefficient is kept by every mask under insertion and dropped by every
+ * mask under deletion. out: band-major coefficients of sets * (n_iter + 1) items, item (s, m) =
+ * s * (n_iter + 1) + m, i.e. out[sets * (n_iter + 1) * off[b] + (s * (n_iter + 1) + m) * n_b + e] =
+ * coeffs[sets * off[b] + s * n_b + e] * keep: the buffer wam_waverec reads with batch =
+ * sets * (n_iter + 1). n_iter >= 1, n_comp >= 0, rank_len >= 1. */
+int wam_rank_mask_coeffs(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
+                         int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
+                         float* out, void* stream);
+/* The same selection on flat rows with the identity slot map (the mel target): src [sets, len]
+ * float32, rank [sets, len] int32, out [sets, n_iter + 1, len] float32:
+ * out[s, m, i] = src[s, i] * keep(rank[s, i], m) with rank_len = len. */
+int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_t* rank, int64_t n_iter,
+                       int64_t n_comp, int deletion, float* out, void* stream);
+/* Peak normalisation of `rows` rows of `len` float32 (numpy's wf / wf.max() per reconstruction):
+ * mx[r] = the signed maximum of row r (not of its absolute values); out[r, i] = in[r, i] / mx[r] in
+ * IEEE fp32 division (correctly rounded, no reciprocal multiply); silent[r] (int32, device, may be
+ * NULL) = 1 when mx[r] == 0 and 0 otherwise. A silent row divides by zero as IEEE does: 0 / 0 = NaN,
+ * a negative value / 0 = -inf. With zero_silent != 0 a silent row is copied unchanged instead. out
+ * may be `in` (in place). Inputs are finite: a NaN input is ignored by the maximum and an all-NaN
+ * row has mx = -inf; neither is part of the contract. */
+int wam_peak_normalize(int64_t rows, int64_t len, const float* in, float* out, int32_t* silent, int zero_silent,
+                       void* stream);
+
 /* WaveletAttribution3D.visualize (lib/wam_3D.py:662-719): cube [items, S, S, S]
  * float32 (the |grad| cube of smooth / IG) -> out [items, levels + 2, S, S, S] float32: per level
  * the block (approximation corner, or add + ada + add + daa + dad + dda of the detail shell, as

@@ -87,6 +87,9 @@ _SIGS = {
     "wam_gaussian_filter2d": (c_int, [c_i64, c_int, c_int, c_dp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "wam_upsample_masks": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wam_masked_sums": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wam_rank_mask_coeffs": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
+    "wam_rank_mask_rows": (c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
+    "wam_peak_normalize": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_vp]),
     "wam_ew_bias_act": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int, c_vp]),
     "wam_ew_add_bias_relu": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wam_ew_relu_mask": (c_int, [c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -31,6 +31,9 @@ GPU), ``tie_order='numpy'`` ranks on the host with np.argsort like the reference
 Transform: the default (Resize((224, 224)) -- a no-op for 224 x 224 reconstructions --, ToTensor,
 Normalize(ImageNet)) runs fused on the GPU; a user ``transform`` (a callable on HWC uint8 numpy
 images) is applied on the host instead.
+
+The audio evaluator ``Eval1DWAM`` (``src/evaluators.py:39-306``: insertion / deletion on wavelet
+coefficients or the mel spectrogram, faithfulness of spectra, input fidelity) closes the module.
 """
 import ctypes
 import math
@@ -42,7 +45,10 @@ from scipy.ndimage import zoom
 from scipy.stats import spearmanr
 
 from ._lib import c_f32, check, lib, ptr, stream_of
+from .melspec import kernel_supported, mel_forward, melspec_db
 from .plan import get_plan
+from .wam_1D import WaveletAttribution1D
+from .wam_1D import _peak_normalise as _peak_normalise_1d
 from .wam_2D import WaveletAttribution2D
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -363,3 +369,208 @@ class Eval2DWAM(WaveletAttribution2D):
         up, _ = self._upsample(source_masks, grid_size, tuple(image.shape[1:]))
         ys = self._evaluate_batched(self._altered_inputs(image, up), label, batch_size)
         return source_masks[int(np.argmin(ys)), :, :]
+
+
+# ====================================================================================== audio
+def coeff_slot_map(length, levels, band_lens, n_masks=1):
+    """The mask slot of every coefficient of a clip of `length` samples, as Eval1DWAM places its
+    mask slices (src/evaluators.py:76-127): band i (coarse to fine, band_lens[i] = n_i coefficients)
+    takes mask columns r[i] : max(r[i + 1], n_i) with r = [0, int(length / 2^J), ..., int(length / 2),
+    length] -- offsets from the waveform length, not the bands' own running lengths -- clipped at the
+    mask length sum(n_i). A slice n_i - 1 wide is padded on the right with one column (slot -1); any
+    other width is numpy's broadcast ValueError of the reference's coeff * mask (n_masks only words
+    the message). Returns int32 [sum(n_i)]."""
+    total = int(sum(band_lens))
+    r = [0] + [int(length / 2 ** j) for j in range(levels, -1, -1)]
+    parts = []
+    for i, n_i in enumerate(band_lens):
+        start, end = r[i], min(max(r[i + 1], n_i), total)
+        width = max(0, end - start)
+        if width != n_i:
+            width += 1  # np.pad(..., ((0, 0), (0, 1)))
+            if width != n_i:
+                raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,%d)"
+                                 % (n_i, n_masks, width))
+            parts.append(np.concatenate([np.arange(start, end), [-1]]))
+        else:
+            parts.append(np.arange(start, end))
+    return np.concatenate(parts).astype(np.int32)
+
+
+class Eval1DWAM(WaveletAttribution1D):
+    """src/evaluators.py:39-306 -- insertion / deletion on the wavelet coefficients or on the mel
+    spectrogram, faithfulness of spectra (Parekh et al.) and input fidelity (Paissan et al.) of an
+    audio WAM, on the device. Same positional arguments, methods, return values and side attributes
+    (``grad_wams`` computed once and cached, ``insertion_curves``, ``deletion_curves``).
+
+    Per group of clips (``eval_batch`` model rows per forward, several clips' masks in one):
+
+      wam_wavedec (ptwt's default mode 'reflect', not ``mode``) --ranks of |coefficient gradients| on
+      the device--> wam_rank_mask_coeffs (all n_iter + 1 masked sets, band-major; the masks are never
+      stored) --wam_waverec (one launch)--> wam_peak_normalize (wf / wf.max(), signed maximum)
+      --mel front-end (k_mel_fwd where it applies, else the torch path)--> model (no grad)
+
+    and for the mel target wam_rank_mask_rows on the clips' own dB mel spectrograms. Host work left:
+    the softmax and AUC on [n_iter + 1, classes] logits, the ``tie_order='numpy'`` ranking.
+
+    Kept from the reference: the mask slices are placed at offsets taken from the waveform length
+    (coeff_slot_map; at 4004 samples they sit one slot off the gradients' own layout, at 4002 band 1
+    takes a pad column that is 1 under insertion and 0 under deletion, every non-haar wavelet is a
+    ValueError); the wavelet target ranks |g|, the mel target the signed gradient; the last mask is
+    forced full. The all-zero mask reconstructs silence and 0 / 0 makes that row NaN, so every
+    wavelet-target insertion / deletion score is NaN (``silent='nan'``, the default); k_mel_fwd's
+    clamp would swallow a NaN waveform, so the rows wam_peak_normalize flags get NaN logits after
+    the forward. ``silent='zero'`` leaves such a row silent and the scores finite. Ties: numpy's
+    argsort is not stable; ``tie_order`` as in Eval2DWAM."""
+
+    def __init__(self, model, batch_size=128, wavelet="haar", J=3, method="smooth", mode="reflect", device=None,
+                 approx_coeffs=False, n_mels=128, n_fft=1024, sample_rate=44100, n_samples=25, stdev_spread=0.001,
+                 random_seed=42, *, tie_order="stable", eval_batch=520, silent="nan", **wam_kw):
+        super().__init__(model, wavelet, J, method, mode, device, approx_coeffs, n_mels, n_fft, sample_rate, n_samples,
+                         stdev_spread, random_seed)
+        self.grad_wams = None
+        self.batch_size = batch_size
+        self.gradwam = WaveletAttribution1D(model, wavelet=wavelet, J=J, method=method, mode=mode, device=device,
+                                            approx_coeffs=approx_coeffs, n_mels=n_mels, n_fft=n_fft,
+                                            sample_rate=sample_rate, n_samples=n_samples, stdev_spread=stdev_spread,
+                                            random_seed=random_seed, **wam_kw)
+        if tie_order not in ("stable", "numpy"):
+            raise ValueError("tie_order must be 'stable' or 'numpy'")
+        if silent not in ("nan", "zero"):
+            raise ValueError("silent must be 'nan' or 'zero'")
+        self.tie_order = tie_order
+        self.eval_batch = eval_batch
+        self.silent = silent
+        self.insertion_curve = []   # the reference's constructor names
+        self.deletion_curve = []
+        self.insertion_curves = []
+        self.deletion_curves = []
+
+    # -------------------------------------------------------------------- device pipeline
+    def _ranks(self, values):
+        """values [sets, len] (host): rank[s, p] = position of slot p in set s's descending order."""
+        values = np.ascontiguousarray(values)
+        if self.tie_order == "numpy":
+            order = torch.as_tensor(np.stack([np.argsort(v)[::-1] for v in values])).to(self._dev)
+        else:
+            order = torch.argsort(torch.as_tensor(values).to(self._dev), dim=1, stable=True).flip(1)
+        rank = torch.empty_like(order)
+        rank.scatter_(1, order, torch.arange(order.shape[1], device=self._dev).expand_as(order))
+        return rank.to(torch.int32).contiguous()
+
+    def _slot_map(self, plan, n_masks):
+        key = ("slots1d", plan, self._dev)
+        if key not in _LAYOUT:
+            pos = coeff_slot_map(plan.shape[0], self.J, [s[0] for s in plan.band_shapes], n_masks)
+            _LAYOUT[key] = torch.as_tensor(pos).to(self._dev)
+        return _LAYOUT[key]
+
+    def _mel(self, wave):
+        if kernel_supported(self.n_fft, self.n_mels):
+            return mel_forward(wave, self.n_fft, self.sample_rate, self.n_mels).unsqueeze(1)
+        return melspec_db(wave, self.n_fft, self.sample_rate, self.n_mels)
+
+    def auc_from_wavelet(self, gradients, waveform, sample, mode, n_iter):
+        """src/evaluators.py:56-143 for the clips `sample` (an index or a sequence of indices) of
+        `waveform` [N, W]: the dB mel spectrograms [len(sample) * (n_iter + 1), 1, T, n_mels] of the
+        peak-normalised reconstructions of every masked coefficient set, on the device. The rows
+        whose reconstruction is silent are left in ``self._silent_rows`` (bool, device)."""
+        dev = self._dev
+        samples = [sample] if np.isscalar(sample) else list(sample)
+        wave = torch.as_tensor(waveform).detach().to(dev, torch.float32)
+        # the reference's call hands over the clip itself (x[sample]); a batch is indexed here
+        wave = (wave[None] if wave.dim() == 1 else wave[samples]).contiguous()
+        sets, M = len(samples), n_iter + 1
+        plan = get_plan(1, (wave.shape[-1],), self.J, self.wavelet, "reflect", dev)  # ptwt.wavedec's default mode
+        pos = self._slot_map(plan, M)
+        K = plan.coeff_numel
+        g = np.stack([np.concatenate([np.asarray(b)[s] for b in gradients]) for s in samples])
+        if g.shape[1] != K:
+            raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,%d)" % (K, M, g.shape[1]))
+        rank = self._ranks(np.abs(g))
+        coeffs = plan.wavedec(wave)
+        masked = torch.empty(sets * M * K, dtype=torch.float32, device=dev)
+        check(lib.wam_rank_mask_coeffs(plan.handle, sets, ptr(coeffs), ptr(rank), K, ptr(pos), n_iter, int(K / n_iter),
+                                       int(mode == "deletion"), ptr(masked), stream_of(dev)))
+        rec = plan.waverec(masked, sets * M)[0].view(sets * M, -1)
+        flags = torch.empty(sets * M, dtype=torch.int32, device=dev)
+        check(lib.wam_peak_normalize(sets * M, rec.shape[1], ptr(rec), ptr(rec), ptr(flags),
+                                     int(self.silent == "zero"), stream_of(dev)))
+        self._silent_rows = flags.bool()
+        return self._mel(rec)
+
+    def auc_from_melspec(self, melspec, source_melspec, mode, n_iter):
+        """src/evaluators.py:145-176 for one clip ([T, n_mels] gradients and dB mel spectrogram) or a
+        batch of clips ([sets, T, n_mels]): [sets * (n_iter + 1), 1, T, n_mels] on the device."""
+        dev = self._dev
+        grad = np.asarray(melspec)
+        grad = grad.reshape((-1,) + grad.shape[-2:])
+        src = torch.as_tensor(source_melspec).detach().to(dev, torch.float32).reshape(grad.shape).contiguous()
+        sets, n = grad.shape[0], grad.shape[1] * grad.shape[2]
+        rank = self._ranks(grad.reshape(sets, n))  # the signed gradient (generate_masks has no abs)
+        out = torch.empty((sets * (n_iter + 1), 1) + grad.shape[1:], dtype=torch.float32, device=dev)
+        check(lib.wam_rank_mask_rows(sets, n, ptr(src), ptr(rank), n_iter, int(n / n_iter), int(mode == "deletion"),
+                                     ptr(out), stream_of(dev)))
+        self._silent_rows = None
+        return out
+
+    # -------------------------------------------------------------------- reference API
+    def evaluate_auc(self, x, y, mode, target, n_iter=64, argmax=False):
+        """src/evaluators.py:178-235."""
+        if isinstance(x, list):
+            x = _peak_normalise_1d(x)
+        if self.grad_wams is None:
+            self.grad_wams = self.gradwam(x, y)
+        dev = self._dev
+        xd = torch.as_tensor(x).detach().to(dev, torch.float32).contiguous()
+        melspecs, gradients = self.grad_wams
+        n_sounds = xd.shape[0]
+        M = n_iter + 1
+        scores, predicted_probs, raw_preds = [], [], []
+        per_call = max(1, self.eval_batch // M)
+        with torch.no_grad():
+            source = self._mel(xd) if target == "melspec" else None
+            for s0 in range(0, n_sounds, per_call):
+                group = list(range(s0, min(n_sounds, s0 + per_call)))
+                if target == "melspec":
+                    inputs = self.auc_from_melspec(np.asarray(melspecs)[group], source[group], mode, n_iter)
+                elif target == "wavelet":
+                    inputs = self.auc_from_wavelet(gradients, xd, group, mode, n_iter)
+                else:
+                    raise ValueError("target must be 'wavelet' or 'melspec', got %r" % (target,))
+                logits = self.model(inputs).float()
+                if self._silent_rows is not None and self.silent == "nan":
+                    logits[self._silent_rows] = float("nan")
+                preds = logits.cpu().numpy()
+                for k, s in enumerate(group):
+                    p = preds[k * M:(k + 1) * M]
+                    raw_preds.append(p)
+                    prob = _softmax(p)[:, y[s]]
+                    scores.append(compute_auc(prob))
+                    predicted_probs.append(prob)
+        if argmax:
+            return raw_preds
+        return scores, predicted_probs
+
+    def insertion(self, x, y, target, n_iter):
+        scores, predicted_probs = self.evaluate_auc(x, y, "insertion", target, n_iter)
+        self.insertion_curves = predicted_probs
+        return scores
+
+    def deletion(self, x, y, target, n_iter):
+        scores, predicted_probs = self.evaluate_auc(x, y, "deletion", target, n_iter)
+        self.deletion_curves = predicted_probs
+        return scores
+
+    def faithfulness_of_spectra(self, x, y, target):
+        """src/evaluators.py:247-277: the drop of the class probability when the more important half
+        of the components is deleted (deletion with n_iter = 2, p[0] - p[1])."""
+        _, predicted_probs = self.evaluate_auc(x, y, "deletion", target, 2)
+        predicted_probs = np.array(predicted_probs)
+        return (predicted_probs[:, 0] - predicted_probs[:, 1]).tolist()
+
+    def input_fidelity(self, x, y, target):
+        """src/evaluators.py:279-306: arg-max classes with the more important half and with all of the
+        components inserted (insertion with n_iter = 2, rows 1 and 2)."""
+        preds = np.array(self.evaluate_auc(x, y, "insertion", target, 2, argmax=True))
+        return np.argmax(preds[:, 1:, :], axis=2).tolist()

@@ -111,6 +111,16 @@ int wam_waverec_adjoint(const wam_plan* plan, int64_t batch, const float* grad, 
 enum wam_caps { WAM_CAP_NOISY_WAVEDEC = 1, WAM_CAP_ADJOINT_MAPS = 2, WAM_CAP_BF16_NHWC = 4 };
 /* which fused entry points below this plan supports (bit set of wam_caps) */
 int wam_plan_caps(const wam_plan* plan);
+/* which kernel family serves each transform of this plan, as one NUL-terminated line in buf (cap
+ * bytes; 512 hold any plan), e.g.
+ *   ana=plane|rows,rows,rows adj=plane|rows,rows,rows syn=plane|colstrip maps=plane caps=7
+ * ana (wam_wavedec), adj (wam_waverec_adjoint): the whole-transform route (none, plane, tile1,
+ * haar3), then after '|' the route of every level, finest first (rows, colstrip, tile3, axis), which
+ * serves plans without a whole-transform route and calls that route declines (e.g. a buffer that
+ * is not 16-byte aligned); syn (wam_waverec): the same with one route for all levels; maps: the fused
+ * wam_waverec_adjoint_maps pass (none, plane, rows); caps: wam_plan_caps. Works on host-only plans.
+ * WAM_ERR_INVALID_ARG when buf is too small. */
+int wam_plan_describe(const wam_plan* plan, char* buf, int cap);
 
 /* SmoothGrad sample generation fused into the first analysis level (lib/wam_2D.py:390-406):
  * coeffs of x_i + sigma_i * N(0,1) for n_samples x images x channels planes, with the same

@@ -65,6 +65,7 @@ _SIGS = {
     "wam_reproject_scales": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "wam_disentangle_scales": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "wam_plan_caps": (c_int, [c_vp]),
+    "wam_plan_describe": (c_int, [c_vp, ctypes.c_char_p, c_int]),
     "wam_wavedec_noisy": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp]),
     "wam_wavedec_noisy_ex": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, ctypes.c_uint64, c_i64, c_i64, c_vp, c_vp,
                                      c_vp]),

@@ -57,6 +57,26 @@ __host__ __device__ __forceinline__ int wam_ext_index(int i, int n, int mode) {
 enum { WAM_F_ANA_LO = 0, WAM_F_ANA_HI = 1, WAM_F_SYN_LO = 2, WAM_F_SYN_HI = 3, WAM_F_ADJ_LO = 4,
        WAM_F_ADJ_HI = 5, WAM_F_COUNT = 6 };
 
+// Which kernel family serves each transform of a plan: resolved once by plan_geometry (plan.hip
+// resolve_routes, the only place that combines the families' *_supported predicates with the plan
+// flags) and read by the drivers, wam_plan_caps, wam_plan_workspace_bytes and wam_plan_describe.
+// A whole-transform route runs every level in one launch; the per-level routes serve plans without
+// one, and calls the whole-transform launcher declines.
+enum WamWhole : uint8_t { WAM_WHOLE_NONE, WAM_WHOLE_PLANE, WAM_WHOLE_TILE1, WAM_WHOLE_HAAR3 };
+enum WamLevel : uint8_t { WAM_LVL_AXIS, WAM_LVL_ROWS, WAM_LVL_COLSTRIP, WAM_LVL_TILE3 };
+enum WamMaps : uint8_t { WAM_MAPS_NONE, WAM_MAPS_PLANE, WAM_MAPS_ROWS };
+struct WamRoutes {
+  struct Ana {
+    WamWhole whole;
+    WamLevel level[WAM_MAX_LEVELS];      // 0 = finest
+  } ana, adj;                            // wavedec; adjoint of waverec
+  WamWhole syn;
+  WamLevel syn_level;                    // colstrip, tile3 or axis: the same at every level
+  WamMaps maps;                          // the fused adjoint + maps pass
+  bool maps_coop;                        // the plane maps pass runs COOP: it takes bf16 gradients
+  bool noise0;                           // level 0 of the analysis takes fused SmoothGrad noise
+};
+
 struct wam_plan {
   int ndim;
   int levels;
@@ -76,7 +96,9 @@ struct wam_plan {
   float* d_filt;                         // WAM_F_COUNT * L floats on the device
   float h_filt[WAM_F_COUNT][WAM_MAX_FILT];
   int device;
-  int flags;                             // WAM_PLAN_GENERIC: force the per-axis kernels
+  int flags;                             // wam_plan_flags: GENERIC / NO_ROWS / NO_PLANE narrow the routes,
+                                         // NO_COOP / FORCE_COOP pick the plane kernels' level-1 form
+  WamRoutes routes;
 };
 
 static inline int64_t wam_prod(const int64_t* d, int n) {

@@ -14,8 +14,6 @@
 // percent. Boundary modes: zero, reflect, symmetric, constant (periodic extensions are not local
 // and stay on the per-axis kernels).
 #include <algorithm>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -24,20 +22,6 @@
 namespace {
 
 typedef float f2v __attribute__((ext_vector_type(2)));  // packed fp32 (v_pk_fma_f32)
-
-// opt in to more than 64 KB of dynamic LDS, once per (kernel, device)
-int lds_opt_in(const void* kern, int bytes) {
-  static std::mutex mu;
-  static std::set<std::pair<const void*, int>> done;
-  if (bytes <= 64 * 1024) return WAM_OK;
-  int dev = 0;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.count({kern, dev})) return WAM_OK;
-  WAM_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  done.insert({kern, dev});
-  return WAM_OK;
-}
 
 constexpr int kT1 = 512;          // threads per workgroup (analysis)
 constexpr int kT1S = 256;         // threads per workgroup (synthesis)
@@ -945,8 +929,7 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
         ((uintptr_t)in & 15))
       return WAM_ERR_UNSUPPORTED;
   }
-  const WamNoise none{nullptr, 1, 1, 0, 0, 0, 0};
-  const WamNoise& NZ = nz ? *nz : none;
+  const WamNoise& NZ = nz ? *nz : kNoNoise;
   const int64_t S = nz ? n_samples : 1;
   const int n = (int)(adjoint ? p->rec_shape[0] : p->lin[0][0]);
   const int mode = adjoint ? WAM_MODE_ZERO : p->mode;
@@ -983,7 +966,7 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
     switch (p->L) {
 #define WAM_D1AIN(LL, NN)                                                                                         \
   {                                                                                                               \
-    if (int rc = lds_opt_in((const void*)k_dwt1_ana_int<LL, NN>, lds_i)) return rc;                              \
+    if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana_int<LL, NN>, kLds1Cap)) return rc;                        \
     int wgs = kAnaWgs;                                                                                            \
     WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_dwt1_ana_int<LL, NN>, kT1, lds_i));         \
     const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);                              \
@@ -1023,7 +1006,7 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
     WamTimer tm(st, nz ? "k_dwt1_ana_p<noise>" : "k_dwt1_ana_p", bytes * (double)(g.tiles - (t_hi - t_lo)) / g.tiles);
     switch (p->L) {
 #define WAM_D1APN(LL, NN)                                                                                      \
-  if (int rc = lds_opt_in((const void*)k_dwt1_ana_p<LL, NN>, lds)) return rc;                                 \
+  if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana_p<LL, NN>, kLds1Cap)) return rc;                            \
   hipLaunchKernelGGL((k_dwt1_ana_p<LL, NN>), dim3((unsigned)grid), dim3(kT1), lds, st, in, coeffs, filt, g, t_lo, \
                      t_hi, nb_blocks, NZ);
 #define WAM_D1AP(LL)                                                                                           \
@@ -1045,7 +1028,7 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
     WamTimer tm(st, nz ? "k_dwt1_ana<noise>" : "k_dwt1_ana", bytes * (double)(g.tiles - (t_hi - t_lo)) / g.tiles);
     switch (p->L) {
 #define WAM_D1AN(LL, NN)                                                                                     \
-  if (int rc = lds_opt_in((const void*)k_dwt1_ana<LL, NN>, lds)) return rc;                                 \
+  if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana<LL, NN>, kLds1Cap)) return rc;                           \
   hipLaunchKernelGGL((k_dwt1_ana<LL, NN>), dim3((unsigned)nb_blocks), dim3(kT1), lds, st, in, coeffs, filt, g, \
                      t_lo, t_hi, NZ);
 #define WAM_D1A(LL)                                                                                          \
@@ -1099,7 +1082,7 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
 #define WAM_D1SI(LL, JJ)                                                                                        \
   if (p->L == LL && g.J == JJ) {                                                                                \
     using Sh = SynShape<LL, JJ>;                                                                                \
-    if (int e = lds_opt_in((const void*)k_dwt1_syn_int<LL, JJ>, Sh::lds_bytes)) return e;                        \
+    if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_int<LL, JJ>, kLds1Cap)) return e;                        \
     hipLaunchKernelGGL((k_dwt1_syn_int<LL, JJ>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs, o, \
                        filt, g, nout, sc, t_lo, t_hi, units);                                                  \
     rc = WAM_OK;                                                                                                \
@@ -1122,7 +1105,7 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
     switch (p->L) {
 #define WAM_D1S(LL)                                                                                            \
   case LL:                                                                                                     \
-    if (int rc = lds_opt_in((const void*)k_dwt1_syn<LL>, lds)) return rc;                                      \
+    if (int rc = wam_lds_opt_in((const void*)k_dwt1_syn<LL>, kLds1Cap)) return rc;                                   \
     hipLaunchKernelGGL(k_dwt1_syn<LL>, dim3((unsigned)nb_blocks), dim3(kT1S), lds, st, coeffs, o, filt, g, nout, sc, \
                        t_lo, t_hi);                                                                            \
     break;

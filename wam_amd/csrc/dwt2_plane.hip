@@ -23,7 +23,6 @@
 // Workgroup order: an XCD-aware bijective swizzle makes consecutive logical workgroups share an
 // XCD (L2); for noisy analysis the logical order is sample-fastest, so the S noise samples of one
 // clean plane run back to back on one XCD and its rows are read from HBM about once.
-#include <atomic>
 
 #include "rowtools.hpp"
 
@@ -1054,15 +1053,7 @@ int launch_plane_t(const PlaneGeom& g, int lds_bytes, int64_t n_items, const flo
                    const float* filt, const WamNoise& nz, int64_t S, int64_t group_items, const char* name,
                    double bytes, hipStream_t st) {
   auto kern = k_plane_ana<L, CPL, NOISE, MC, MAPS, COOP, IN, PW>;
-  static std::atomic<uint64_t> attr_set{0};  // opt in to > 64 KB of dynamic LDS, once per device
-  int dev = 0;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    WAM_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kPlaneLdsCap));
-    attr_set.fetch_or(bit);
-  }
+  if (int rc = wam_lds_opt_in((const void*)kern, kPlaneLdsCap)) return rc;
   WamTimer tm(st, name, bytes);
   hipLaunchKernelGGL(kern, dim3((unsigned)n_items), dim3(64 * PW), lds_bytes, st, in, out, band_max, filt, g, nz, n_items,
                      S, group_items);
@@ -1097,15 +1088,14 @@ int dispatch_maps_bf16(const wam_plan* p, const PlaneGeom& g, int lds_bytes, int
                        float* out, float* band_max, const float* filt, int64_t group_items, double bytes,
                        hipStream_t st) {
   if (!g.coop) return WAM_ERR_UNSUPPORTED;
-  const WamNoise nz{nullptr, 1, 1, 0, 0, 0, 0};
   const bool two = g.mw[0] > 64;
   const char* name = IN == kInBf16Nhwc ? "k_plane_maps<bf16nhwc>" : "k_plane_maps<bf16>";
 #define WAM_MAPS_CASE(LL)                                                                                          \
   case LL:                                                                                                         \
     return two ? launch_plane_t<LL, 2, false, MC, true, true, IN>(g, lds_bytes, n_items, in, out, band_max, filt,  \
-                                                                   nz, 1, group_items, name, bytes, st)             \
+                                                                   kNoNoise, 1, group_items, name, bytes, st)       \
                : launch_plane_t<LL, 1, false, MC, true, true, IN>(g, lds_bytes, n_items, in, out, band_max, filt,  \
-                                                                   nz, 1, group_items, name, bytes, st);
+                                                                   kNoNoise, 1, group_items, name, bytes, st);
   switch (p->L) {
     WAM_MAPS_CASE(2) WAM_MAPS_CASE(4) WAM_MAPS_CASE(6) WAM_MAPS_CASE(8)
     default: return WAM_ERR_UNSUPPORTED;
@@ -1144,8 +1134,7 @@ int launch_dwt2_plane_analysis(const wam_plan* p, int64_t items, const float* in
     return dispatch_plane<true, 0, false>(p, g, lds_bytes, items, in, coeffs, nullptr, filt, *nz, n_samples, 1,
                                           "k_plane_ana<noise>", bytes, st);
   }
-  const WamNoise none{nullptr, 1, 1, 0, 0, 0, 0};
-  return dispatch_plane<false, 0, false>(p, g, lds_bytes, items, in, coeffs, nullptr, filt, none, 1, 1,
+  return dispatch_plane<false, 0, false>(p, g, lds_bytes, items, in, coeffs, nullptr, filt, kNoNoise, 1, 1,
                                          "k_plane_ana", bytes, st);
 }
 
@@ -1159,7 +1148,6 @@ int launch_dwt2_plane_maps(const wam_plan* p, int64_t images, int channels, int6
   PlaneGeom g = make_geom(p, nh0, nw0, WAM_MODE_ZERO, images);
   int rowlds, llcap;
   const int lds_bytes = lds_floats(p, nw0, rowlds, llcap) * 4;
-  const WamNoise none{nullptr, 1, 1, 0, 0, 0, 0};
   const double bytes = (double)images * ((in_fmt ? 2.0 : 4.0) * channels * nh0 * nw0 +
                                           4.0 * (double)p->band_off[p->nbands]);
   if (in_fmt == kInBf16Nhwc && channels == 3)
@@ -1169,9 +1157,9 @@ int launch_dwt2_plane_maps(const wam_plan* p, int64_t images, int channels, int6
   if (in_fmt != kInF32)  // one channel: the two bf16 layouts coincide
     return dispatch_maps_bf16<1, kInBf16Nchw>(p, g, lds_bytes, images, grad, maps, band_max, filt, group_items, bytes, st);
   if (channels == 3)
-    return dispatch_plane<false, 3, true>(p, g, lds_bytes, images, grad, maps, band_max, filt, none, 1, group_items,
+    return dispatch_plane<false, 3, true>(p, g, lds_bytes, images, grad, maps, band_max, filt, kNoNoise, 1, group_items,
                                           "k_plane_maps", bytes, st);
-  return dispatch_plane<false, 1, true>(p, g, lds_bytes, images, grad, maps, band_max, filt, none, 1, group_items,
+  return dispatch_plane<false, 1, true>(p, g, lds_bytes, images, grad, maps, band_max, filt, kNoNoise, 1, group_items,
                                         "k_plane_maps", bytes, st);
 }
 
@@ -1200,15 +1188,7 @@ template <int L, int OC>
 int launch_syn_plane_t(const SynGeom& g, int lds_bytes, int64_t n_items, const float* coeffs, void* out,
                        const float* filt, const SynAlphas& al, double bytes, hipStream_t st) {
   auto kern = k_plane_syn<L, OC>;
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    WAM_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kPlaneLdsCap));
-    attr_set.fetch_or(bit);
-  }
+  if (int rc = wam_lds_opt_in((const void*)kern, kPlaneLdsCap)) return rc;
   WamTimer tm(st, OC ? "k_plane_syn<bf16nhwc>" : "k_plane_syn", bytes);
   hipLaunchKernelGGL(kern, dim3((unsigned)n_items), dim3(kPT), lds_bytes, st, coeffs, out, filt, g, al, n_items);
   WAM_LAUNCH_CHECK();

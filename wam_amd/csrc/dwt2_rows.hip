@@ -497,7 +497,7 @@ int launch_ana_rows_t(int64_t batch, const float* in, int nh, int nw, int mh, in
   int nchunks, R;
   pick_chunks(batch * nstrips, mh, nchunks, R);
   const int64_t waves = batch * nstrips * nchunks;
-  WamNoise z = nz ? *nz : WamNoise{nullptr, 1, 1, 0, 0, 0, 0};
+  WamNoise z = nz ? *nz : kNoNoise;
   double bytes = 4.0 * ((double)batch * 4.0 * mh * mw + (nz ? (double)z.images * z.channels : (double)batch) * nh * nw);
   WamTimer tm(st, NOISE ? "k_ana_rows<noise>" : "k_ana_rows", bytes);
   hipLaunchKernelGGL((k_ana_rows<L, CPL, VEC, MAXV, NOISE>), dim3((unsigned)((waves + kWaves - 1) / kWaves)),

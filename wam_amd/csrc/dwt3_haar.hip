@@ -306,13 +306,12 @@ int launch_dwt3_haar_analysis(const wam_plan* p, int64_t batch, const float* in,
   if (grid > 0x7fffffff) return WAM_ERR_UNSUPPORTED;
   const float* filt = p->d_filt + (adjoint ? WAM_F_ADJ_LO : WAM_F_ANA_LO) * p->L;  // lo0 lo1 hi0 hi1
   WamTimer tm(st, "k_haar3_ana", 4.0 * (double)batch * ((double)g.D * g.H * g.W + (double)p->band_off[p->nbands]));
-  const WamNoise none{nullptr, 1, 1, 0, 0, 0, 0};
   if (p->levels == 1)
     hipLaunchKernelGGL((k_haar3_ana<1, false>), dim3((unsigned)grid), dim3(kT3), 0, st, in, coeffs, filt, g, blocks,
-                       none, (int64_t)1);
+                       kNoNoise, (int64_t)1);
   else
     hipLaunchKernelGGL((k_haar3_ana<2, false>), dim3((unsigned)grid), dim3(kT3), 0, st, in, coeffs, filt, g, blocks,
-                       none, (int64_t)1);
+                       kNoNoise, (int64_t)1);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

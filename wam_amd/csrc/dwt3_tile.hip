@@ -261,8 +261,11 @@ int launch_syn3(const Tile3Geom& g0, const Tile3Bands& b, float* out, const floa
 }
 
 bool tile3_ok(const wam_plan* p) {
-  return p->ndim == 3 && p->L >= 2 && p->L <= 8 && !(p->L & 1) && p->pad == p->L - 2 &&
-         !(p->flags & WAM_PLAN_GENERIC);
+  if (p->ndim != 3 || p->L < 2 || p->L > 8 || (p->L & 1) || p->pad != p->L - 2) return false;
+  // 32-bit tile coordinates: every level's sizes stay below 2^30 when the reconstruction's do
+  for (int a = 0; a < 3; ++a)
+    if (p->rec_shape[a] >= (int64_t(1) << 30)) return false;
+  return true;
 }
 
 }  // namespace

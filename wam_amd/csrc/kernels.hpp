@@ -1,6 +1,25 @@
 // Internal launch interfaces shared between the translation units of libwam_hip.so.
 #pragma once
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "common.hpp"
+
+// Opt a kernel in to more than 64 KB of dynamic LDS, once per (kernel, device). cap_bytes is the
+// LDS cap of the kernel's file, never one call's byte count: every later plan that passes the
+// file's own support check then launches on the same instantiation.
+inline int wam_lds_opt_in(const void* kern, int cap_bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  WAM_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  if (done.count({kern, dev})) return WAM_OK;
+  WAM_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, cap_bytes));
+  done.insert({kern, dev});
+  return WAM_OK;
+}
 
 // Logical workgroup id under which consecutive ids run on one XCD. Workgroup b is observed to land
 // on XCD b % 8 (round robin; not a contract, so only locality depends on it): the bijection maps
@@ -91,6 +110,7 @@ struct WamNoise {
   int64_t sample_base;
   int64_t image_base;     // global index of image 0 (Philox counter word; batch-sharded ranks)
 };
+constexpr WamNoise kNoNoise{nullptr, 1, 1, 0, 0, 0, 0};  // the argument of the kernels built without noise
 
 // plane-resident multi-level 2D analysis (dwt2_plane.hip): all levels of a plane in one workgroup
 bool dwt2_plane_supported(const wam_plan* p, bool adjoint);

@@ -24,8 +24,6 @@
 #include "kernels.hpp"
 
 #include <algorithm>
-#include <mutex>
-#include <set>
 
 namespace {
 
@@ -676,19 +674,6 @@ int lds_fwd(int log_n, int n_mels, int nnz) {
   return (log_n <= 10 ? tab_floats(N, n_mels, nnz, false) * 4 : 0) + kWavesF * (M + (M >> 4) + 2) * 8;
 }
 
-int lds_opt_in_mel(const void* kern, int bytes) {
-  static std::mutex mu;
-  static std::set<std::pair<const void*, int>> done;
-  if (bytes <= 64 * 1024) return WAM_OK;
-  int dev = 0;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.count({kern, dev})) return WAM_OK;
-  WAM_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  done.insert({kern, dev});
-  return WAM_OK;
-}
-
 int check_args(int64_t items, int64_t samples, int n_fft, int n_mels, int nnz, int* log_n) {
   if (items < 0 || n_mels < 1 || nnz < 0) return WAM_ERR_INVALID_ARG;
   int l = 0;
@@ -733,7 +718,7 @@ extern "C" int wam_melspec(int64_t items, int64_t samples, int n_fft, int n_mels
   switch (log_n) {
 #define WAM_MELF(L)                                                                                           \
   case L:                                                                                                     \
-    if (int rc = lds_opt_in_mel((const void*)k_mel_fwd<L, (L <= 10)>, lds)) return rc;                        \
+    if (int rc = wam_lds_opt_in((const void*)k_mel_fwd<L, (L <= 10)>, kMaxLds)) return rc;                    \
     hipLaunchKernelGGL((k_mel_fwd<L, (L <= 10)>), dim3(grid), dim3(64 * kWavesF), lds, st, g, wave, tables, index, \
                        out);                                                                                  \
     break;
@@ -777,8 +762,8 @@ extern "C" int wam_melspec_adjoint(int64_t items, int64_t samples, int n_fft, in
 #undef WAM_MELR
     default: return WAM_ERR_UNSUPPORTED;
   }
-  if (int rc = lds_opt_in_mel(kern, lds)) return rc;
-  if (int rc = lds_opt_in_mel(kfold, lds)) return rc;
+  if (int rc = wam_lds_opt_in(kern, kMaxLds)) return rc;
+  if (int rc = wam_lds_opt_in(kfold, kMaxLds)) return rc;
   int dev = 0, cus = 256, per_cu = 1;
   WAM_HIP_CHECK(hipGetDevice(&dev));
   WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));

@@ -6,15 +6,52 @@
 //   more at the end when the next finer coefficient is one shorter (ptwt
 //   _adjust_padding_at_reconstruction)
 //   adjoint of synthesis = zero-padded analysis with reverse(rec) filters.
-// 2D transforms run on the fused LDS kernels in dwt2_fused.hip; 1D / 3D (and 2D with filters
-// longer than the fused kernels support) run on the generic per-axis kernels in dwt_axis.hip.
+// Kernel families: 1D dwt1_tile.hip; 2D dwt2_plane.hip (all levels in one workgroup), dwt2_rows.hip
+// (row-resident levels) and dwt2_fused.hip (column strips); 3D dwt3_haar.hip and dwt3_tile.hip; any
+// plan on the per-axis kernels of dwt_axis.hip. resolve_routes picks among them once per plan
+// (WamRoutes in common.hpp); the drivers, the caps and the workspace size below only read that table,
+// and wam_plan_describe prints it.
 #include <stdlib.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "kernels.hpp"
+
+// The one place that combines the kernel families' *_supported predicates (each checks its own
+// ndim) with the plan flags. The plan arrives zeroed: no whole-transform route, every level on the
+// per-axis kernels, no maps pass -- which is all a WAM_PLAN_GENERIC plan gets.
+static void resolve_routes(wam_plan* p) {
+  WamRoutes& r = p->routes;
+  if (p->flags & WAM_PLAN_GENERIC) return;
+  const bool rows_ok = !(p->flags & WAM_PLAN_NO_ROWS);
+  const bool plane_ok = rows_ok && !(p->flags & WAM_PLAN_NO_PLANE);
+  const WamLevel below_rows = dwt2_fused_supported(p) ? WAM_LVL_COLSTRIP
+                              : dwt3_tile_supported(p) ? WAM_LVL_TILE3
+                                                       : WAM_LVL_AXIS;
+  bool adj_rows_all = true;
+  for (int adjoint = 0; adjoint < 2; ++adjoint) {
+    WamRoutes::Ana& a = adjoint ? r.adj : r.ana;
+    if (plane_ok && dwt2_plane_supported(p, adjoint)) a.whole = WAM_WHOLE_PLANE;
+    else if (dwt1_tile_supported(p, adjoint)) a.whole = WAM_WHOLE_TILE1;
+    else if (dwt3_haar_supported(p)) a.whole = WAM_WHOLE_HAAR3;
+    for (int l = 0; l < p->levels; ++l) {
+      a.level[l] = rows_ok && dwt2_rows_supported(p, l, adjoint) ? WAM_LVL_ROWS : below_rows;
+      if (adjoint && a.level[l] != WAM_LVL_ROWS) adj_rows_all = false;
+    }
+  }
+  if (plane_ok && dwt2_plane_syn_supported(p)) r.syn = WAM_WHOLE_PLANE;
+  else if (dwt1_tile_supported(p, false)) r.syn = WAM_WHOLE_TILE1;
+  else if (dwt3_haar_supported(p)) r.syn = WAM_WHOLE_HAAR3;
+  r.syn_level = below_rows;
+  r.maps = r.adj.whole == WAM_WHOLE_PLANE ? WAM_MAPS_PLANE : adj_rows_all ? WAM_MAPS_ROWS : WAM_MAPS_NONE;
+  r.maps_coop = r.maps == WAM_MAPS_PLANE && dwt2_plane_maps_coop(p);
+  // fused noise counts groups of 4 elements along the last axis; the kernels that take it are the
+  // whole-transform ones (single-channel signals and volumes in 1D / 3D) and the level-0 row kernel
+  r.noise0 = (r.ana.whole != WAM_WHOLE_NONE || r.ana.level[0] == WAM_LVL_ROWS) && p->lin[0][p->ndim - 1] % 4 == 0;
+}
 
 extern "C" {
 
@@ -38,7 +75,8 @@ int wam_plan_create(wam_plan** out, int ndim, const int64_t* shape, int levels, 
   return wam_plan_create_ex(out, ndim, shape, levels, dec_lo, dec_hi, rec_lo, rec_hi, L, mode, 0);
 }
 
-// geometry of a plan (sizes per level, crop flags, band layout, fp32 filters): host arithmetic only
+// geometry of a plan (sizes per level, crop flags, band layout, fp32 filters, kernel routes): host
+// arithmetic only
 static int plan_geometry(wam_plan* p, int ndim, const int64_t* shape, int levels, const double* dec_lo,
                          const double* dec_hi, const double* rec_lo, const double* rec_hi, int L, int mode,
                          int flags) {
@@ -109,6 +147,7 @@ static int plan_geometry(wam_plan* p, int ndim, const int64_t* shape, int levels
     p->h_filt[WAM_F_ADJ_LO][k] = (float)rec_lo[k];
     p->h_filt[WAM_F_ADJ_HI][k] = (float)rec_hi[k];
   }
+  resolve_routes(p);
   return WAM_OK;
 }
 
@@ -178,6 +217,36 @@ int wam_plan_rec_shape(const wam_plan* p, int64_t* dims) {
   return WAM_OK;
 }
 
+int wam_plan_caps(const wam_plan* p) {
+  if (!p) return 0;
+  const WamRoutes& r = p->routes;
+  int caps = 0;
+  if (r.noise0) caps |= WAM_CAP_NOISY_WAVEDEC;
+  if (r.maps != WAM_MAPS_NONE) caps |= WAM_CAP_ADJOINT_MAPS;
+  // the bf16 NHWC model hand-off: plane-resident synthesis and the COOP maps pass of the plane kernel
+  if (r.syn == WAM_WHOLE_PLANE && r.maps_coop) caps |= WAM_CAP_BF16_NHWC;
+  return caps;
+}
+
+int wam_plan_describe(const wam_plan* p, char* buf, int cap) {
+  if (!p || !buf || cap < 1) return WAM_ERR_INVALID_ARG;
+  static const char* const whole[] = {"none", "plane", "tile1", "haar3"};
+  static const char* const level[] = {"axis", "rows", "colstrip", "tile3"};
+  static const char* const maps[] = {"none", "plane", "rows"};
+  const WamRoutes& r = p->routes;
+  std::string s;
+  for (int adjoint = 0; adjoint < 2; ++adjoint) {
+    const WamRoutes::Ana& a = adjoint ? r.adj : r.ana;
+    s += std::string(adjoint ? " adj=" : "ana=") + whole[a.whole] + "|";
+    for (int l = 0; l < p->levels; ++l) s += std::string(l ? "," : "") + level[a.level[l]];
+  }
+  s += std::string(" syn=") + whole[r.syn] + "|" + level[r.syn_level] + " maps=" + maps[r.maps] +
+       " caps=" + std::to_string(wam_plan_caps(p));
+  if ((int)s.size() >= cap) return WAM_ERR_INVALID_ARG;
+  memcpy(buf, s.c_str(), s.size() + 1);
+  return WAM_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
@@ -226,13 +295,6 @@ int sub_of_key(int nd, int key) {
 
 }  // namespace
 
-// 2D plans whose waverec runs the per-level row synthesis (k_dwt2_syn) rather than the
-// plane-resident kernel: their IG alphas are synthesised kSynWsAlpha per level launch
-static bool syn_rows_alpha_batched(const wam_plan* p) {
-  return p->ndim == 2 && !(p->flags & WAM_PLAN_GENERIC) && dwt2_fused_supported(p) &&
-         ((p->flags & (WAM_PLAN_NO_ROWS | WAM_PLAN_NO_PLANE)) || !dwt2_plane_syn_supported(p));
-}
-
 // floats per synthesis LL slot (the largest intermediate approximation of the batch), rounded up
 // to 4 floats: slots stay 16-byte aligned, so the float2 output stores of the row synthesis
 // (rowtools.hpp syn_stream, vec2 on even level widths) land on 8-byte aligned addresses whatever
@@ -264,8 +326,10 @@ extern "C" int64_t wam_plan_workspace_bytes(const wam_plan* p, int64_t batch) {
   int64_t tmp_s = generic_syn_tmp(p, batch);
   int64_t a_side = 2 * ll + tmp_a;
   int64_t s_side = 2 * rec_ll + tmp_s;
-  // row-synthesis 2D plans: the LL ping-pong of kSynWsAlpha alphas per level launch
-  if (syn_rows_alpha_batched(p) && 2 * kSynWsAlpha * rec_ll > s_side) s_side = 2 * kSynWsAlpha * rec_ll;
+  // plans whose waverec runs the per-level column-strip synthesis (k_dwt2_syn) rather than the
+  // plane-resident kernel: the LL ping-pong of the kSynWsAlpha IG alphas of one level launch
+  const bool alpha_batched = p->routes.syn != WAM_WHOLE_PLANE && p->routes.syn_level == WAM_LVL_COLSTRIP;
+  if (alpha_batched && 2 * kSynWsAlpha * rec_ll > s_side) s_side = 2 * kSynWsAlpha * rec_ll;
   int64_t elems = a_side > s_side ? a_side : s_side;
   return (elems + 64) * (int64_t)sizeof(float);
 }
@@ -380,36 +444,30 @@ void band_ptrs(const wam_plan* p, int64_t batch, float* coeffs, int level, float
   for (int k = 0; k < per; ++k) sub[k] = coeffs + batch * p->band_off[wam_band_of(p, level, k)];
 }
 
-bool use_rows(const wam_plan* p, int level, bool adjoint) {
-  return p->ndim == 2 && !(p->flags & (WAM_PLAN_GENERIC | WAM_PLAN_NO_ROWS)) && dwt2_rows_supported(p, level, adjoint);
-}
-
-bool use_plane(const wam_plan* p, bool adjoint) {
-  return p->ndim == 2 && !(p->flags & (WAM_PLAN_GENERIC | WAM_PLAN_NO_ROWS | WAM_PLAN_NO_PLANE)) &&
-         dwt2_plane_supported(p, adjoint);
-}
-
-bool use_colstrip(const wam_plan* p) {
-  return p->ndim == 2 && !(p->flags & WAM_PLAN_GENERIC) && dwt2_fused_supported(p);
-}
-
 // noise (level 0 only): fused SmoothGrad noise on the load; `batch` then counts the virtual
 // (sample, image, channel) planes and x holds the clean (image, channel) planes.
 int analysis_driver(const wam_plan* p, int64_t batch, const float* x, float* coeffs, void* ws, hipStream_t st,
                     bool adjoint, const WamNoise* noise = nullptr, int64_t n_samples = 1) {
-  if (use_plane(p, adjoint)) {  // all levels in one launch, LL pyramid in LDS
-    int rc = launch_dwt2_plane_analysis(p, batch, x, coeffs, adjoint, noise, n_samples, st);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
+  const WamRoutes::Ana& r = adjoint ? p->routes.adj : p->routes.ana;
+  // A whole-transform launcher may decline a call (WAM_ERR_UNSUPPORTED) for reasons that are no
+  // property of the plan -- an input that is not 16-byte aligned, a grid over 2^31, a noise layout
+  // it does not take: the call then runs on the per-level routes. This is the only fallback of the
+  // drivers in this file; every other launcher's status is final.
+  int whole = WAM_ERR_UNSUPPORTED;
+  switch (r.whole) {
+    case WAM_WHOLE_PLANE:  // all levels in one launch, LL pyramid in LDS
+      whole = launch_dwt2_plane_analysis(p, batch, x, coeffs, adjoint, noise, n_samples, st);
+      break;
+    case WAM_WHOLE_TILE1:  // all levels per signal tile
+      whole = launch_dwt1_tile_analysis(p, batch, x, coeffs, adjoint, st, noise, n_samples);
+      break;
+    case WAM_WHOLE_HAAR3:  // all levels per block
+      whole = noise ? launch_dwt3_haar_analysis_noisy(p, batch, x, coeffs, noise, n_samples, st)
+                    : launch_dwt3_haar_analysis(p, batch, x, coeffs, adjoint, st);
+      break;
+    case WAM_WHOLE_NONE: break;
   }
-  if (p->ndim == 1 && !(p->flags & WAM_PLAN_GENERIC)) {  // all levels per signal tile
-    int rc = launch_dwt1_tile_analysis(p, batch, x, coeffs, adjoint, st, noise, n_samples);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
-  }
-  if (p->ndim == 3 && !(p->flags & WAM_PLAN_GENERIC)) {  // Haar: all levels per block
-    int rc = noise ? launch_dwt3_haar_analysis_noisy(p, batch, x, coeffs, noise, n_samples, st)
-                   : launch_dwt3_haar_analysis(p, batch, x, coeffs, adjoint, st);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
-  }
+  if (whole != WAM_ERR_UNSUPPORTED) return whole;
   int nd = p->ndim;
   float* w = (float*)ws;
   int64_t ll = batch * wam_prod(p->lout[0], nd);
@@ -425,19 +483,21 @@ int analysis_driver(const wam_plan* p, int64_t batch, const float* x, float* coe
     band_ptrs(p, batch, coeffs, l, sub);
     float* out_a = (l == p->levels - 1) ? coeffs : llbuf[l & 1];
     const WamNoise* nz = (l == 0) ? noise : nullptr;
-    int rc;
-    if (use_rows(p, l, adjoint)) {
-      rc = launch_dwt2_analysis_rows(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, nz, st);
-    } else if (nz) {
-      rc = WAM_ERR_UNSUPPORTED;
-    } else if (use_colstrip(p)) {
-      rc = launch_dwt2_analysis_fused(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, st);
-    } else {
-      rc = WAM_ERR_UNSUPPORTED;
-      if (p->ndim == 3 && dwt3_tile_supported(p))  // all three axes of the level in one pass
+    if (nz && r.level[l] != WAM_LVL_ROWS) return WAM_ERR_UNSUPPORTED;  // no other level kernel fuses noise
+    int rc = WAM_ERR_UNSUPPORTED;
+    switch (r.level[l]) {
+      case WAM_LVL_ROWS:
+        rc = launch_dwt2_analysis_rows(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, nz, st);
+        break;
+      case WAM_LVL_COLSTRIP:
+        rc = launch_dwt2_analysis_fused(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, st);
+        break;
+      case WAM_LVL_TILE3:  // all three axes of the level in one pass
         rc = launch_dwt3_analysis_tile(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, st);
-      if (rc == WAM_ERR_UNSUPPORTED)
+        break;
+      case WAM_LVL_AXIS:
         rc = generic_analysis_level(p, batch, cur, in_dims, p->lout[l], mode, fset, out_a, sub, tmp, st);
+        break;
     }
     if (rc) return rc;
     cur = out_a;
@@ -462,24 +522,6 @@ int wam_waverec_adjoint(const wam_plan* p, int64_t batch, const float* grad, flo
   return analysis_driver(p, batch, grad, coeff_grads, ws, (hipStream_t)stream, true);
 }
 
-int wam_plan_caps(const wam_plan* p) {
-  if (!p) return 0;
-  int caps = 0;
-  bool rows_all = true;
-  for (int l = 0; l < p->levels; ++l) rows_all = rows_all && use_rows(p, l, true);
-  if (rows_all || use_plane(p, true)) caps |= WAM_CAP_ADJOINT_MAPS;
-  if (use_plane(p, false) || (use_rows(p, 0, false) && p->lin[0][1] % 4 == 0)) caps |= WAM_CAP_NOISY_WAVEDEC;
-  if (p->ndim == 1 && !(p->flags & WAM_PLAN_GENERIC) && dwt1_tile_supported(p, false) && p->lin[0][0] % 4 == 0)
-    caps |= WAM_CAP_NOISY_WAVEDEC;  // single-channel signals (channels != 1: WAM_ERR_UNSUPPORTED)
-  if (p->ndim == 3 && !(p->flags & WAM_PLAN_GENERIC) && dwt3_haar_supported(p) && p->lin[0][2] % 4 == 0)
-    caps |= WAM_CAP_NOISY_WAVEDEC;  // single-channel volumes (channels != 1: WAM_ERR_UNSUPPORTED)
-  // the bf16 NHWC model hand-off: plane-resident synthesis and the COOP maps pass of the plane kernel
-  if (p->ndim == 2 && !(p->flags & (WAM_PLAN_GENERIC | WAM_PLAN_NO_ROWS | WAM_PLAN_NO_PLANE)) &&
-      dwt2_plane_syn_supported(p) && use_plane(p, true) && dwt2_plane_maps_coop(p))
-    caps |= WAM_CAP_BF16_NHWC;
-  return caps;
-}
-
 int wam_wavedec_noisy_ex(const wam_plan* p, int64_t n_samples, int64_t images, int channels, const float* x,
                          const float* sigma, uint64_t seed, int64_t sample_base, int64_t image_base, float* coeffs,
                          void* ws, void* stream) {
@@ -501,18 +543,23 @@ int wam_waverec_adjoint_maps(const wam_plan* p, int64_t groups, int64_t group_it
                              float* maps, float* band_max, float* coeff_grads, void* ws, void* stream) {
   if (!p || !p->d_filt || !grad || !maps || !band_max || !ws || groups < 0 || group_items < 0 || channels < 1)
     return WAM_ERR_INVALID_ARG;
-  if (!(wam_plan_caps(p) & WAM_CAP_ADJOINT_MAPS) || (channels != 1 && channels != 3)) return WAM_ERR_UNSUPPORTED;
+  const WamRoutes& r = p->routes;
+  if (r.maps == WAM_MAPS_NONE || (channels != 1 && channels != 3)) return WAM_ERR_UNSUPPORTED;
   const int64_t images = groups * group_items;
   if (images == 0) return WAM_OK;
   hipStream_t st = (hipStream_t)stream;
   const int64_t planes = images * channels;
-  if (use_plane(p, true)) {
+  if (r.maps == WAM_MAPS_PLANE) {
     // maps from the channel-mean gradient (one pass); per-channel grads only when asked for
     int rc = launch_dwt2_plane_maps(p, images, channels, group_items, grad, 0, maps, band_max, st);
     if (rc != WAM_ERR_UNSUPPORTED) {
       if (rc || !coeff_grads) return rc;
       return analysis_driver(p, planes, grad, coeff_grads, ws, st, true);
     }
+    // a declined call (as in analysis_driver: a gradient that is not 16-byte aligned) takes the row
+    // kernels below, which need every level of the adjoint on them
+    for (int l = 0; l < p->levels; ++l)
+      if (r.adj.level[l] != WAM_LVL_ROWS) return WAM_ERR_UNSUPPORTED;
   }
   // per level (rows kernels): maps from the channel mean taken on the level-0 load (the plane
   // kernels' form: one plane filtered per image at every level); the per-channel coefficient
@@ -567,24 +614,22 @@ int wam_waverec(const wam_plan* p, int64_t batch, const float* coeffs, const flo
   if (!alpha && n_alpha != 1) return WAM_ERR_INVALID_ARG;
   if (batch == 0) return WAM_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (p->ndim == 2 && !(p->flags & (WAM_PLAN_GENERIC | WAM_PLAN_NO_ROWS | WAM_PLAN_NO_PLANE)) &&
-      dwt2_plane_syn_supported(p)) {  // all levels and all alphas in one launch
-    int rc = launch_dwt2_plane_synthesis(p, batch, coeffs, alpha, n_alpha, out, 0, st);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
+  const WamRoutes& r = p->routes;
+  int whole = WAM_ERR_UNSUPPORTED;  // a declined call runs per level (see analysis_driver)
+  switch (r.syn) {
+    case WAM_WHOLE_PLANE:  // all levels and all alphas in one launch
+      whole = launch_dwt2_plane_synthesis(p, batch, coeffs, alpha, n_alpha, out, 0, st);
+      break;
+    case WAM_WHOLE_TILE1: whole = launch_dwt1_tile_synthesis(p, batch, coeffs, alpha, n_alpha, out, st); break;
+    case WAM_WHOLE_HAAR3: whole = launch_dwt3_haar_synthesis(p, batch, coeffs, alpha, n_alpha, out, st); break;
+    case WAM_WHOLE_NONE: break;
   }
-  if (p->ndim == 1 && !(p->flags & WAM_PLAN_GENERIC)) {
-    int rc = launch_dwt1_tile_synthesis(p, batch, coeffs, alpha, n_alpha, out, st);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
-  }
-  if (p->ndim == 3 && !(p->flags & WAM_PLAN_GENERIC)) {
-    int rc = launch_dwt3_haar_synthesis(p, batch, coeffs, alpha, n_alpha, out, st);
-    if (rc != WAM_ERR_UNSUPPORTED) return rc;
-  }
+  if (whole != WAM_ERR_UNSUPPORTED) return whole;
   int nd = p->ndim;
   int64_t out_item = wam_prod(p->rec_shape, nd);
   const int64_t rec_ll = syn_ll_stride(p, batch);
   float* w = (float*)ws;
-  if (nd == 2 && !(p->flags & WAM_PLAN_GENERIC) && dwt2_fused_supported(p)) {
+  if (r.syn_level == WAM_LVL_COLSTRIP) {
     // alphas in groups: one launch per level per group, each level's detail bands read once per
     // group; the group's intermediate LL planes ping-pong between two workspace sets
     const int64_t ws_elems = wam_plan_workspace_bytes(p, batch) / (int64_t)sizeof(float) - 64;
@@ -621,79 +666,15 @@ int wam_waverec(const wam_plan* p, int64_t batch, const float* coeffs, const flo
       float* sub[7];
       band_ptrs(p, batch, (float*)coeffs, l, sub);
       float* dst = (l == 0) ? out + (int64_t)ai * batch * out_item : abuf[c & 1];
-      int rc = WAM_ERR_UNSUPPORTED;
-      if (nd == 3 && dwt3_tile_supported(p))  // all three axes of the level in one pass
-        rc = launch_dwt3_synthesis_tile(p, batch, l, a_cur, a_scale, sub, s, dst, st);
-      if (rc == WAM_ERR_UNSUPPORTED) rc = generic_synthesis_level(p, batch, l, a_cur, a_scale, sub, s, dst, tmp, st);
+      const int rc = r.syn_level == WAM_LVL_TILE3  // all three axes of the level in one pass
+                         ? launch_dwt3_synthesis_tile(p, batch, l, a_cur, a_scale, sub, s, dst, st)
+                         : generic_synthesis_level(p, batch, l, a_cur, a_scale, sub, s, dst, tmp, st);
       if (rc) return rc;
       a_cur = dst;
       a_scale = 1.0f;
     }
   }
   return WAM_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Live per-launch timing (see timing.hpp)
-// ------------------------------------------------------------------------------------------------
-#include <atomic>
-#include <mutex>
-
-namespace {
-struct TimingRec {
-  const char* name;
-  hipEvent_t s, e;
-  double bytes;
-};
-std::atomic<int> g_timing{0};
-std::mutex g_timing_mu;
-std::vector<TimingRec> g_timing_recs;
-}  // namespace
-
-WamTimer::WamTimer(hipStream_t st_, const char* name_, double bytes_) : st(st_), name(name_), bytes(bytes_) {
-  if (!g_timing.load(std::memory_order_relaxed)) return;
-  if (hipEventCreate(&s) != hipSuccess || hipEventCreate(&e) != hipSuccess) {
-    s = e = nullptr;
-    return;
-  }
-  (void)hipEventRecord(s, st);
-}
-
-WamTimer::~WamTimer() {
-  if (!s) return;
-  (void)hipEventRecord(e, st);
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  g_timing_recs.push_back({name, s, e, bytes});
-}
-
-extern "C" {
-
-int wam_timing_enable(int on) {
-  g_timing.store(on ? 1 : 0);
-  return WAM_OK;
-}
-
-int wam_timing_drain(int max_records, char* names, float* ms, double* bytes) {
-  if (max_records < 0 || (max_records > 0 && (!names || !ms || !bytes))) return -WAM_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  int n = 0;
-  for (auto& r : g_timing_recs) {
-    if (n < max_records) {
-      float t = 0.f;
-      if (hipEventSynchronize(r.e) == hipSuccess) (void)hipEventElapsedTime(&t, r.s, r.e);
-      strncpy(names + 64 * n, r.name, 63);
-      names[64 * n + 63] = 0;
-      ms[n] = t;
-      bytes[n] = r.bytes;
-      ++n;
-    }
-    (void)hipEventDestroy(r.s);
-    (void)hipEventDestroy(r.e);
-  }
-  g_timing_recs.clear();
-  return n;
 }
 
 }  // extern "C"

@@ -140,6 +140,14 @@ class Plan:
     def caps(self):
         return lib.wam_plan_caps(self._h)
 
+    @property
+    def routes(self):
+        """The kernel family serving each transform of this plan (wam_plan_describe), e.g.
+        'ana=plane|rows,rows,rows adj=plane|rows,rows,rows syn=plane|colstrip maps=plane caps=7'."""
+        buf = ctypes.create_string_buffer(512)
+        check(lib.wam_plan_describe(self._h, buf, len(buf)))
+        return buf.value.decode()
+
     def wavedec_noisy(self, x, sigma, n_samples, images, channels, seed, sample_base=0, out=None, image_base=0):
         """coefficients of x + sigma_i N(0,1) (Philox) for n_samples x images x channels planes;
         image_base = global index of x's first image (Philox counter of a batch-sharded rank)."""

@@ -385,6 +385,63 @@ int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_
 int wam_peak_normalize(int64_t rows, int64_t len, const float* in, float* out, int32_t* silent, int zero_silent,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * WAMAnalyzer2D (src/analyzers.py:16-203, src/analyzers_helpers.py:6-134): necessary components
+ * (quantile thresholds on the WAM map) and scale isolation (one mask per level). The reference's
+ * per-image, per-quantile CPU loop (3 x pywt.wavedec2 -> coeffs_to_array -> arr * (grad_wam >= t) ->
+ * waverec2, then ((x - mn) / mx - mn) * 255 -> uint8 -> PIL -> transform) becomes: wam_wavedec (mode
+ * symmetric) once for all images, wam_threshold_mask_coeffs, one wam_waverec,
+ * wam_quantize_normalize_ex. The masks themselves are never stored.
+ * ---------------------------------------------------------------------------------------------- */
+/* Value thresholds to masked coefficients. plan: a 2D plan (WAM_ERR_UNSUPPORTED otherwise) with K =
+ * wam_plan_coeff_numel values per plane. coeffs: band-major coefficients of images * channels planes
+ * as wam_wavedec writes them, plane (n, c) = n * channels + c (band b of plane i starts at
+ * images * channels * off[b] + i * n_b, off[b] = wam_plan_band_offset, n_b the band's element count).
+ * pos [K] int32 (device), shared by all planes: pos[k] = the row-major position, in a size x size
+ * array, of the coefficient at per-plane offset k (pywt.coeffs_to_array's layout). wam [images,
+ * size * size] float64 (device): the map of each image. thr (device, float64): the n_thr thresholds
+ * of image n are thr[n * thr_stride + q], q = 0 .. n_thr - 1 (thr_stride >= n_thr).
+ * For coefficient k of plane (n, c) and threshold q, with p = pos[k] and v = wam[n, p]:
+ *   level_mode == 0: keep = strict ? v > thr[n, q] : v >= thr[n, q], compared in float64 (a NaN v
+ *     is never kept);
+ *   level_mode != 0: threshold q is level entry q of compute_levelized_masks, n_thr = levels + 1 <=
+ *     17, edges (HOST int32 [n_thr], read during the call) = int(size / 2^j), j = 0 .. levels. With
+ *     (r, c) = (p / size, p % size) and m = max(r, c), entry q < levels is the region edges[q + 1] <=
+ *     m < edges[q] (the three blocks [s:e, s:e], [s:e, :s], [:s, s:e]) and entry `levels` the region
+ *     m < edges[levels]; v is replaced by 0.0 when p lies outside entry q's region, then compared as
+ *     above.
+ * A position outside [0, size * size) is kept by no threshold. out: band-major coefficients of
+ * images * n_thr * channels planes, plane (n, q, c) = (n * n_thr + q) * channels + c:
+ *   out[images * n_thr * channels * off[b] + ((n * n_thr + q) * channels + c) * n_b + e] =
+ *   coeffs[images * channels * off[b] + (n * channels + c) * n_b + e] * (keep ? 1.0f : 0.0f)
+ * (a dropped negative value is -0.0f, a dropped NaN stays NaN, as numpy's arr * mask): the buffer
+ * wam_waverec reads with batch = images * n_thr * channels. images <= 0, n_thr <= 0 or thr_stride <
+ * n_thr: WAM_ERR_INVALID_ARG. That size * size equals the array size of pos is the caller's check. */
+int wam_threshold_mask_coeffs(const wam_plan* plan, int64_t images, int channels, const float* coeffs,
+                              const int32_t* pos, int size, const double* wam, int64_t n_thr, const double* thr,
+                              int64_t thr_stride, int level_mode, const int32_t* edges, int strict, float* out,
+                              void* stream);
+/* Quantisation of `images` reconstructions (channels <= 4 planes of `plane` floats each), mn / mx =
+ * the minimum / maximum over all channels of the image, every operation an IEEE float32
+ * round-to-nearest one in the order written:
+ *   rule 0: s = ((x - mn) / (mx - mn)) * 255; q = 0 when s is NaN, else s truncated (s is in
+ *     [0, 255]): wam_quantize_normalize's rule, `out` bit-identical to it;
+ *   rule 1: s = (((x - mn) / mx) - mn) * 255 (src/analyzers.py:155, the reference's precedence); q =
+ *     numpy's float32 -> uint8 cast on x86: s truncated toward zero to int32, the low 8 bits kept
+ *     (-3.7 -> 253, 300.7 -> 44, 1000.3 -> 232); q = 0 when s is NaN, infinite or |s| >= 2^31.
+ * u8 (may be NULL): q as bytes, planar [images, channels, plane]. out (may be NULL; not both):
+ * (q / 255 - mean[c]) / std[c] as float32 [images, channels, plane]; mean / std are HOST arrays of
+ * `channels` values (needed only with out). */
+int wam_quantize_normalize_ex(int64_t images, int channels, int64_t plane, const float* rec, int rule,
+                              const float* mean, const float* std, uint8_t* u8, float* out, void* stream);
+/* wam_quantize_resize_normalize with the quantisation rule of wam_quantize_normalize_ex in front
+ * (rule 0: bit-identical to it); every other argument as there. */
+int wam_quantize_resize_normalize_ex(int64_t images, int channels, int in_h, int in_w, const float* rec, int rule,
+                                     int out_h, int out_w, int ksize_h, const int32_t* bounds_h, const int32_t* kk_h,
+                                     int ksize_v, const int32_t* bounds_v, const int32_t* kk_v, int y0, int tmp_h,
+                                     const float* mean, const float* std, uint8_t* scratch, float* out,
+                                     void* stream);
+
 /* WaveletAttribution3D.visualize (lib/wam_3D.py:662-719): cube [items, S, S, S]
  * float32 (the |grad| cube of smooth / IG) -> out [items, levels + 2, S, S, S] float32: per level
  * the block (approximation corner, or add + ada + add + daa + dad + dda of the detail shell, as

@@ -16,7 +16,8 @@ from .wam_1D import BaseWAM1D, VisualizerWAM1D, WaveletAttribution1D
 from .wam_2D import BaseWAM2D, WaveletAttribution2D
 from .wam_3D import BaseWAM3D, WaveletAttribution3D
 from .evaluation import Eval1DWAM, Eval2DWAM
+from .analysis import WAMAnalyzer2D
 
 __all__ = ["WaveletDetailTuple2d", "wavedec", "waverec", "wavedec2", "waverec2", "wavedec3", "waverec3",
            "BaseWAM1D", "WaveletAttribution1D", "VisualizerWAM1D", "BaseWAM2D", "WaveletAttribution2D", "BaseWAM3D",
-           "WaveletAttribution3D", "Eval1DWAM", "Eval2DWAM"]
+           "WaveletAttribution3D", "Eval1DWAM", "Eval2DWAM", "WAMAnalyzer2D"]

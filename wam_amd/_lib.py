@@ -91,6 +91,13 @@ _SIGS = {
     "wam_rank_mask_coeffs": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "wam_rank_mask_rows": (c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "wam_peak_normalize": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_vp]),
+    "wam_threshold_mask_coeffs": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_int,
+                                          ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_vp]),
+    "wam_quantize_normalize_ex": (c_int, [c_i64, c_int, c_i64, c_vp, c_int, ctypes.POINTER(c_f32),
+                                          ctypes.POINTER(c_f32), c_vp, c_vp, c_vp]),
+    "wam_quantize_resize_normalize_ex": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                                 c_vp, c_int, c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_f32),
+                                                 ctypes.POINTER(c_f32), c_vp, c_vp, c_vp]),
     "wam_ew_bias_act": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int, c_vp]),
     "wam_ew_add_bias_relu": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wam_ew_relu_mask": (c_int, [c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1,0 +1,336 @@
+// WAMAnalyzer2D (src/analyzers.py:16-203, helpers src/analyzers_helpers.py:6-134): which coefficients
+// the model needs (isolate_necessary_components: quantile thresholds on the WAM map) and what each
+// scale contributes (isolate_scales: one mask per level). Per image and per quantile the reference
+// runs pywt.wavedec2 -> coeffs_to_array -> arr * (grad_wam >= t) -> waverec2 per channel on the CPU,
+// then its own quantisation ((x - mn) / mx - mn) * 255 -> uint8 (wrapping) -> PIL -> transform. Here the
+// analysis runs once for all images, one pass turns the thresholds into the masked band-major
+// coefficients of every (image, threshold, channel) plane wam_waverec reads -- the masks are never
+// stored -- and one workgroup per reconstruction does the min / max reduction and the quantisation.
+// Both kernels are HBM-bound streaming passes.
+#include "kernels.hpp"
+
+namespace {
+
+constexpr int kThrChunk = 16;  // thresholds per blockIdx.y (coefficient, position and map value stay in registers)
+
+struct ThrBands {
+  int nbands;
+  int vec[WAM_MAX_BANDS];           // band offset and length are multiples of 4 floats: 16-byte path
+  int64_t off[WAM_MAX_BANDS + 1];   // per-item element offsets
+  int64_t unit0[WAM_MAX_BANDS + 1]; // first work unit of the band (a unit = 4 elements, or 1 on the scalar path)
+};
+
+struct LevelEdges {
+  int n;                            // entries (levels + 1)
+  int e[WAM_MAX_LEVELS + 1];        // int(size / 2^j), j = 0 .. levels
+};
+
+// the map value at array position p of an image; a position outside the map is kept by no threshold
+__device__ __forceinline__ double map_value(const double* __restrict__ w, int32_t p, int64_t map_len) {
+  return ((uint64_t)(int64_t)p < (uint64_t)map_len) ? w[p] : (double)NAN;
+}
+
+// compute_levelized_masks: entry q < levels holds the three blocks [s:e, s:e], [s:e, :s], [:s, s:e] with
+// s = e[q + 1], e = e[q], i.e. s <= max(row, col) < e; entry `levels` holds [:a, :a], a = e[levels].
+// The table is read with constant indices only (it lives in the kernel arguments: a runtime index
+// would copy it to scratch).
+__device__ __forceinline__ void level_bounds(const LevelEdges& le, int q, int& lo, int& hi) {
+  lo = 0;
+  hi = 0;
+  const int qe = q + 1 < le.n ? q : le.n - 1;       // the entry's outer edge
+#pragma unroll
+  for (int j = 0; j <= WAM_MAX_LEVELS; ++j) {
+    if (j == qe) hi = le.e[j];
+    if (j == q + 1 && q + 1 < le.n) lo = le.e[j];
+  }
+}
+
+__device__ __forceinline__ bool in_level(int lo, int hi, int32_t p, int size) {
+  const int r = p / size, c = p - r * size;
+  const int m = r > c ? r : c;
+  return m >= lo && m < hi;
+}
+
+__device__ __forceinline__ float keep_mul(double v, double t, bool strict) {
+  return (strict ? v > t : v >= t) ? 1.f : 0.f;
+}
+
+// One thread owns 4 consecutive coefficients of one (band, input plane) (1 on the scalar path): it
+// reads them, their array positions and the map values there once, and writes them into the
+// kThrChunk threshold items of its blockIdx.y. For one threshold a wave writes 64 x 16 consecutive
+// bytes. LEVEL: threshold q is level entry q, a map value outside the entry's region counts as 0.
+template <bool LEVEL>
+__global__ void __launch_bounds__(256) k_threshold_mask(int64_t images, int channels, ThrBands tb,
+                                                        const float* __restrict__ coeffs,
+                                                        const int32_t* __restrict__ pos, int size,
+                                                        const double* __restrict__ wam, int64_t n_thr,
+                                                        const double* __restrict__ thr, int64_t thr_stride,
+                                                        LevelEdges le, int strict, float* __restrict__ out) {
+  const int64_t planes = images * channels;
+  const int64_t map_len = (int64_t)size * size;
+  const int64_t q0 = (int64_t)blockIdx.y * kThrChunk;
+  const int64_t q1 = q0 + kThrChunk < n_thr ? q0 + kThrChunk : n_thr;
+  const bool st = strict != 0;
+  const int64_t units = tb.unit0[tb.nbands];
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    int b = 0;
+#pragma unroll 1
+    while (b + 1 < tb.nbands && u >= tb.unit0[b + 1]) ++b;
+    const int64_t bo = tb.off[b], bn = tb.off[b + 1] - bo;
+    const int64_t r = u - tb.unit0[b];
+    if (tb.vec[b]) {
+      const int64_t per = bn >> 2;
+      const int64_t pl = r / per, e = (r - pl * per) << 2;
+      const int64_t n = pl / channels, c = pl - n * channels;
+      const wam_f4v cf = *reinterpret_cast<const wam_f4v*>(coeffs + planes * bo + pl * bn + e);
+      const int4 p4 = *reinterpret_cast<const int4*>(pos + bo + e);
+      const int32_t p[4] = {p4.x, p4.y, p4.z, p4.w};
+      const double* w = wam + n * map_len;
+      double v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = map_value(w, p[i], map_len);
+      const double* t = thr + n * thr_stride;
+      float* o = out + planes * n_thr * bo + (n * n_thr * channels + c) * bn + e;
+      for (int64_t q = q0; q < q1; ++q) {
+        const double tq = t[q];
+        int lo = 0, hi = 0;
+        if (LEVEL) level_bounds(le, (int)q, lo, hi);
+        float m[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          double vi = v[i];
+          if (LEVEL && (uint64_t)(int64_t)p[i] < (uint64_t)map_len && !in_level(lo, hi, p[i], size)) vi = 0.0;
+          m[i] = keep_mul(vi, tq, st);
+        }
+        *reinterpret_cast<wam_f4v*>(o + q * channels * bn) = wam_f4v{cf.x * m[0], cf.y * m[1], cf.z * m[2], cf.w * m[3]};
+      }
+    } else {
+      const int64_t pl = r / bn, e = r - pl * bn;
+      const int64_t n = pl / channels, c = pl - n * channels;
+      const float cf = coeffs[planes * bo + pl * bn + e];
+      const int32_t p = pos[bo + e];
+      const double v = map_value(wam + n * map_len, p, map_len);
+      const double* t = thr + n * thr_stride;
+      float* o = out + planes * n_thr * bo + (n * n_thr * channels + c) * bn + e;
+      for (int64_t q = q0; q < q1; ++q) {
+        double vi = v;
+        int lo = 0, hi = 0;
+        if (LEVEL) level_bounds(le, (int)q, lo, hi);
+        if (LEVEL && (uint64_t)(int64_t)p < (uint64_t)map_len && !in_level(lo, hi, p, size)) vi = 0.0;
+        o[q * channels * bn] = cf * keep_mul(vi, t[q], st);
+      }
+    }
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- quantisation of a reconstruction, one workgroup per image (channels x plane floats): the min / max
+// pass, a barrier, then the map on a second read of the image
+__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
+  __shared__ float smn[16], smx[16];
+  for (int s = 32; s > 0; s >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, s, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+  }
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    smn[w] = mn;
+    smx[w] = mx;
+  }
+  __syncthreads();
+  mn = smn[0];
+  mx = smx[0];
+  for (int i = 1; i < nw; ++i) {
+    mn = fminf(mn, smn[i]);
+    mx = fmaxf(mx, smx[i]);
+  }
+}
+
+// RULE 0: normalize_data (src/evaluation_helpers.py:433-435) -> (x * 255).astype(uint8): min-max,
+// values in [0, 255], truncation. A constant image (e.g. insertion step 0: all coefficients masked, a
+// zero reconstruction) gives 0 / 0 = NaN, which numpy's NaN -> uint8 cast turns into 0 on x86
+// (cvttss2si's 0x80000000, low byte 0): pinned here explicitly rather than left to the hardware's
+// float -> int conversion of NaN.
+// RULE 1: the analyzer's ((x - mn) / mx - mn) * 255 (src/analyzers.py:155; the precedence is the
+// reference's), every step a float32 round-to-nearest operation in numpy's order, then numpy's
+// float32 -> uint8 cast as x86 does it: truncation toward zero to int32, the low 8 bits kept (-3.7 ->
+// 253, 300.7 -> 44); NaN and values outside int32 give cvttss2si's 0x80000000, so 0. Pinned
+// explicitly too: the hardware's own conversion saturates.
+template <int RULE>
+__device__ __forceinline__ uint8_t quantize_one(float x, float mn, float mx) {
+  if (RULE == 0) {
+    const float s = __fmul_rn(__fdiv_rn(x - mn, mx - mn), 255.f);
+    return (s != s) ? (uint8_t)0 : (uint8_t)(int)s;
+  }
+  const float s = __fmul_rn(__fsub_rn(__fdiv_rn(__fsub_rn(x, mn), mx), mn), 255.f);
+  if (!(fabsf(s) < 2147483648.f)) return 0;  // NaN, +-inf, beyond int32
+  return (uint8_t)((int)s & 255);
+}
+
+// VEC: plane is a multiple of 4 and the buffers are 16-byte (u8: 4-byte) aligned, so a thread handles 4
+// consecutive values of one channel per step: a 16-byte load, a 4-byte and a 16-byte store. The values are
+// those of the scalar path (the same operations per element; the min / max do not depend on the order).
+template <int RULE, bool VEC>
+__global__ void __launch_bounds__(1024) k_quantize_ex(int channels, int64_t plane, const float* __restrict__ rec,
+                                                      ChanNorm cn, uint8_t* __restrict__ u8,
+                                                      float* __restrict__ out) {
+  const int64_t n = (int64_t)channels * plane;
+  const float* x = rec + blockIdx.x * n;
+  float mn = INFINITY, mx = -INFINITY;
+  if (VEC) {
+    const wam_f4v* x4 = reinterpret_cast<const wam_f4v*>(x);
+    for (int64_t i = threadIdx.x; i < (n >> 2); i += blockDim.x) {
+      const wam_f4v v = x4[i];
+      mn = fminf(fminf(mn, fminf(v.x, v.y)), fminf(v.z, v.w));
+      mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+  } else {
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+      mn = fminf(mn, x[i]);
+      mx = fmaxf(mx, x[i]);
+    }
+  }
+  block_minmax(mn, mx);
+  uint8_t* b = u8 ? u8 + blockIdx.x * n : nullptr;
+  float* o = out ? out + blockIdx.x * n : nullptr;
+  if (VEC) {
+    const wam_f4v* x4 = reinterpret_cast<const wam_f4v*>(x);
+    for (int64_t i = threadIdx.x; i < (n >> 2); i += blockDim.x) {
+      const wam_f4v v = x4[i];
+      const uint8_t q0 = quantize_one<RULE>(v.x, mn, mx), q1 = quantize_one<RULE>(v.y, mn, mx);
+      const uint8_t q2 = quantize_one<RULE>(v.z, mn, mx), q3 = quantize_one<RULE>(v.w, mn, mx);
+      if (b) reinterpret_cast<uchar4*>(b)[i] = make_uchar4(q0, q1, q2, q3);
+      if (o) {
+        const int c = (int)((i << 2) / plane);
+        const float m = cn.mean[c], sd = cn.std[c];
+        reinterpret_cast<wam_f4v*>(o)[i] =
+            wam_f4v{__fdiv_rn(__fdiv_rn((float)q0, 255.f) - m, sd), __fdiv_rn(__fdiv_rn((float)q1, 255.f) - m, sd),
+                    __fdiv_rn(__fdiv_rn((float)q2, 255.f) - m, sd), __fdiv_rn(__fdiv_rn((float)q3, 255.f) - m, sd)};
+      }
+    }
+    return;
+  }
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const uint8_t q = quantize_one<RULE>(x[i], mn, mx);
+    if (b) b[i] = q;
+    if (o) {
+      const int c = (int)(i / plane);
+      o[i] = __fdiv_rn(__fdiv_rn((float)q, 255.f) - cn.mean[c], cn.std[c]);
+    }
+  }
+}
+
+template <int RULE, bool VEC>
+void launch_quantize_as(int64_t images, int channels, int64_t plane, const float* rec, const ChanNorm& cn, uint8_t* u8,
+                        float* out, hipStream_t st) {
+  hipLaunchKernelGGL((k_quantize_ex<RULE, VEC>), dim3((unsigned)images), dim3(1024), 0, st, channels, plane, rec, cn, u8,
+                     out);
+}
+
+int launch_quantize(int64_t images, int channels, int64_t plane, const float* rec, int rule, const float* mean,
+                    const float* std, uint8_t* u8, float* out, hipStream_t st) {
+  ChanNorm cn{};
+  for (int c = 0; c < channels && mean && std; ++c) {
+    cn.mean[c] = mean[c];
+    cn.std[c] = std[c];
+  }
+  const double px = (double)images * channels * plane;
+  const char* name = rule ? "k_quantize_analyzer" : (out ? "k_quantize_normalize" : "k_quantize_u8");
+  const bool vec = (plane & 3) == 0 && aligned16(rec) && (!out || aligned16(out)) &&
+                   (reinterpret_cast<uintptr_t>(u8) & 3) == 0;
+  WamTimer tm(st, name, px * (4.0 + (u8 ? 1.0 : 0.0) + (out ? 4.0 : 0.0)));
+  if (rule) {
+    if (vec) launch_quantize_as<1, true>(images, channels, plane, rec, cn, u8, out, st);
+    else launch_quantize_as<1, false>(images, channels, plane, rec, cn, u8, out, st);
+  } else {
+    if (vec) launch_quantize_as<0, true>(images, channels, plane, rec, cn, u8, out, st);
+    else launch_quantize_as<0, false>(images, channels, plane, rec, cn, u8, out, st);
+  }
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wam_threshold_mask_coeffs(const wam_plan* plan, int64_t images, int channels, const float* coeffs,
+                              const int32_t* pos, int size, const double* wam, int64_t n_thr, const double* thr,
+                              int64_t thr_stride, int level_mode, const int32_t* edges, int strict, float* out,
+                              void* stream) {
+  if (!plan || images <= 0 || n_thr <= 0 || channels < 1 || size < 1 || thr_stride < n_thr || !coeffs || !pos ||
+      !wam || !thr || !out)
+    return WAM_ERR_INVALID_ARG;
+  if (plan->ndim != 2) return WAM_ERR_UNSUPPORTED;
+  if ((int64_t)size * size > INT32_MAX) return WAM_ERR_INVALID_ARG;
+  LevelEdges le{};
+  if (level_mode) {
+    if (!edges || n_thr > WAM_MAX_LEVELS + 1) return WAM_ERR_INVALID_ARG;
+    le.n = (int)n_thr;
+    for (int j = 0; j < le.n; ++j) le.e[j] = edges[j];
+  }
+  const int64_t planes = images * channels;
+  const bool ptrs_aligned = aligned16(coeffs) && aligned16(pos) && aligned16(out);
+  ThrBands tb{};
+  tb.nbands = plan->nbands;
+  int64_t units = 0;
+  for (int b = 0; b < plan->nbands; ++b) {
+    tb.off[b] = plan->band_off[b];
+    const int64_t bn = plan->band_off[b + 1] - plan->band_off[b];
+    tb.vec[b] = ptrs_aligned && (tb.off[b] & 3) == 0 && (bn & 3) == 0;
+    tb.unit0[b] = units;
+    units += planes * (tb.vec[b] ? bn >> 2 : bn);
+  }
+  tb.off[plan->nbands] = plan->band_off[plan->nbands];
+  tb.unit0[plan->nbands] = units;
+  if (units == 0) return WAM_OK;
+  const int64_t K = tb.off[tb.nbands];
+  const int64_t chunks = (n_thr + kThrChunk - 1) / kThrChunk;
+  if (chunks > 65535) return WAM_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  // every input read once (the map at the K positions of each image), every output written once
+  WamTimer tm(st, "k_threshold_mask", 4.0 * planes * K + 4.0 * K + 8.0 * images * K + 8.0 * images * n_thr +
+                                          4.0 * (double)planes * n_thr * K);
+  const dim3 grid(wam_grid(units, 256), (unsigned)chunks);
+  if (level_mode)
+    hipLaunchKernelGGL(k_threshold_mask<true>, grid, dim3(256), 0, st, images, channels, tb, coeffs, pos, size, wam,
+                       n_thr, thr, thr_stride, le, strict, out);
+  else
+    hipLaunchKernelGGL(k_threshold_mask<false>, grid, dim3(256), 0, st, images, channels, tb, coeffs, pos, size, wam,
+                       n_thr, thr, thr_stride, le, strict, out);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int wam_quantize_normalize_ex(int64_t images, int channels, int64_t plane, const float* rec, int rule,
+                              const float* mean, const float* std, uint8_t* u8, float* out, void* stream) {
+  if (images < 0 || images > INT32_MAX || channels < 1 || channels > 4 || plane < 1 || !rec || (rule != 0 && rule != 1) ||
+      (!u8 && !out) || (out && (!mean || !std)))
+    return WAM_ERR_INVALID_ARG;
+  if (images == 0) return WAM_OK;
+  return launch_quantize(images, channels, plane, rec, rule, mean, std, u8, out, (hipStream_t)stream);
+}
+
+int wam_quantize_resize_normalize_ex(int64_t images, int channels, int in_h, int in_w, const float* rec, int rule,
+                                     int out_h, int out_w, int ksize_h, const int32_t* bounds_h, const int32_t* kk_h,
+                                     int ksize_v, const int32_t* bounds_v, const int32_t* kk_v, int y0, int tmp_h,
+                                     const float* mean, const float* std, uint8_t* scratch, float* out,
+                                     void* stream) {
+  if (images < 0 || images > INT32_MAX || channels < 1 || channels > 4 || in_h < 1 || in_w < 1 || out_h < 1 ||
+      out_w < 1 || !rec || (rule != 0 && rule != 1) || !mean || !std || !scratch || !out)
+    return WAM_ERR_INVALID_ARG;
+  const bool horiz = bounds_h != nullptr, vert = bounds_v != nullptr;
+  if ((horiz && (!kk_h || ksize_h < 1)) || (vert && (!kk_v || ksize_v < 1))) return WAM_ERR_INVALID_ARG;
+  if (!horiz && out_w != in_w) return WAM_ERR_SHAPE;
+  if (!vert && out_h != in_h) return WAM_ERR_SHAPE;
+  if (horiz && (y0 < 0 || tmp_h < 1 || y0 + tmp_h > in_h)) return WAM_ERR_SHAPE;
+  if (images == 0) return WAM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_quantize(images, channels, (int64_t)in_h * in_w, rec, rule, nullptr, nullptr, scratch, nullptr, st);
+  if (rc != WAM_OK) return rc;
+  return launch_pil_resize_norm(images, channels, in_h, in_w, out_h, out_w, ksize_h, bounds_h, kk_h, ksize_v, bounds_v,
+                                kk_v, y0, tmp_h, mean, std, scratch, out, st);
+}
+
+}  // extern "C"

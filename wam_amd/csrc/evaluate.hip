@@ -55,57 +55,8 @@ __global__ void __launch_bounds__(256) k_coeff_masks(int64_t items, int64_t n_ma
   }
 }
 
-// ---- normalize_data (:433-435) -> (x * 255).astype(uint8) -> ToTensor (/ 255) -> Normalize:
-// one workgroup per image: min / max over all its channels, then the fused map.
-__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
-  __shared__ float smn[16], smx[16];
-  for (int s = 32; s > 0; s >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, s, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    smn[w] = mn;
-    smx[w] = mx;
-  }
-  __syncthreads();
-  mn = smn[0];
-  mx = smx[0];
-  for (int i = 1; i < nw; ++i) {
-    mn = fminf(mn, smn[i]);
-    mx = fmaxf(mx, smx[i]);
-  }
-}
-
-struct ChanNorm {
-  float mean[4], std[4];
-};
-
-__global__ void __launch_bounds__(1024) k_quantize_normalize(int channels, int64_t plane, const float* __restrict__ rec,
-                                                             ChanNorm cn, float* __restrict__ out) {
-  const int64_t n = (int64_t)channels * plane;
-  const float* x = rec + blockIdx.x * n;
-  float* o = out + blockIdx.x * n;
-  float mn = INFINITY, mx = -INFINITY;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    mn = fminf(mn, x[i]);
-    mx = fmaxf(mx, x[i]);
-  }
-  block_minmax(mn, mx);
-  const float rng = mx - mn;  // numpy: (data - min) / (max - min), float32
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const float v = __fdiv_rn(x[i] - mn, rng);
-    const float s = __fmul_rn(v, 255.f);
-    // astype(uint8): truncation, values in [0, 255]. A constant image (e.g. insertion step 0: all
-    // coefficients masked, a zero reconstruction) gives 0 / 0 = NaN, which numpy's NaN -> uint8 cast
-    // turns into 0 on x86 (cvttss2si's 0x80000000, low byte 0): pinned here explicitly rather than
-    // left to the hardware's float -> int conversion of NaN
-    const float q = (s != s) ? 0.f : (float)(unsigned char)(int)s;
-    const int c = (int)(i / plane);
-    o[i] = __fdiv_rn(__fdiv_rn(q, 255.f) - cn.mean[c], cn.std[c]);
-  }
-}
-
+// ---- the quantisation kernels (normalize_data -> uint8 -> ToTensor -> Normalize) live in analyze2d.hip,
+// which adds the analyzer's rule to them; wam_quantize_normalize calls through with rule 0.
 // ---- torchvision Resize((224, 224)) on the reference's PIL image of a reconstruction that is not
 // 224 x 224 (src/evaluators.py:593-598): normalize_data -> uint8 -> PIL.Image -> Pillow's BILINEAR
 // resample -> ToTensor + Normalize. Pillow's 8-bit resample (libImaging/Resample.c) is integer
@@ -118,25 +69,6 @@ constexpr int kPilBits = 22;
 __device__ __forceinline__ int pil_clip8(int ss) {
   const int v = ss >> kPilBits;
   return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-// one workgroup per image: the min-max quantisation of k_quantize_normalize, written as bytes
-__global__ void __launch_bounds__(1024) k_quantize_u8(int channels, int64_t plane, const float* __restrict__ rec,
-                                                      uint8_t* __restrict__ u8) {
-  const int64_t n = (int64_t)channels * plane;
-  const float* x = rec + blockIdx.x * n;
-  uint8_t* o = u8 + blockIdx.x * n;
-  float mn = INFINITY, mx = -INFINITY;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    mn = fminf(mn, x[i]);
-    mx = fmaxf(mx, x[i]);
-  }
-  block_minmax(mn, mx);
-  const float rng = mx - mn;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const float s = __fmul_rn(__fdiv_rn(x[i] - mn, rng), 255.f);
-    o[i] = (s != s) ? (uint8_t)0 : (uint8_t)(int)s;  // NaN (constant image) -> 0, as numpy on x86
-  }
 }
 
 // horizontal pass: planes of in_h x in_w bytes -> tmp planes of tmp_h x out_w (source rows
@@ -248,6 +180,42 @@ __global__ void __launch_bounds__(256) k_masked_sums(int64_t len, const double* 
 
 }  // namespace
 
+// The two resample passes + ToTensor / Normalize on the bytes the quantisation left in scratch
+// (planes x in_h x in_w, then the horizontal pass's planes x tmp_h x out_w); arguments checked by
+// wam_quantize_resize_normalize_ex (analyze2d.hip), which quantises first.
+int launch_pil_resize_norm(int64_t images, int channels, int in_h, int in_w, int out_h, int out_w, int ksize_h,
+                           const int32_t* bounds_h, const int32_t* kk_h, int ksize_v, const int32_t* bounds_v,
+                           const int32_t* kk_v, int y0, int tmp_h, const float* mean, const float* std,
+                           uint8_t* scratch, float* out, hipStream_t st) {
+  const bool horiz = bounds_h != nullptr, vert = bounds_v != nullptr;
+  ChanNorm cn{};
+  for (int c = 0; c < channels; ++c) {
+    cn.mean[c] = mean[c];
+    cn.std[c] = std[c];
+  }
+  const int64_t planes = images * channels;
+  const int64_t in_px = planes * (int64_t)in_h * in_w;
+  uint8_t* u8 = scratch;                 // planes x in_h x in_w
+  uint8_t* tmp = scratch + in_px;        // planes x tmp_h x out_w (horizontal pass)
+  const uint8_t* vsrc = u8;
+  int vh = in_h;
+  if (horiz) {
+    const int64_t work = planes * (int64_t)tmp_h * out_w;
+    WamTimer tm(st, "k_pil_resize_h", (double)planes * tmp_h * in_w + (double)work);
+    hipLaunchKernelGGL(k_pil_resize_h, dim3(wam_grid(work, 256)), dim3(256), 0, st, planes, in_h, in_w, y0, tmp_h,
+                       out_w, ksize_h, bounds_h, kk_h, u8, tmp);
+    WAM_LAUNCH_CHECK();
+    vsrc = tmp;
+    vh = tmp_h;
+  }
+  const int64_t work = planes * (int64_t)out_h * out_w;
+  WamTimer tm(st, "k_pil_resize_v_norm", (double)planes * vh * out_w + 4.0 * work);
+  hipLaunchKernelGGL(k_pil_resize_v_norm, dim3(wam_grid(work, 256)), dim3(256), 0, st, images, channels, vh, out_h,
+                     out_w, (int)vert, ksize_v, bounds_v, kk_v, vsrc, cn, out);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
 extern "C" {
 
 int wam_rank_masks(int64_t n_iter, int64_t n_comp, int64_t len, const int32_t* rank, int deletion, float* masks,
@@ -280,67 +248,16 @@ int wam_coeff_masks(const wam_plan* plan, int64_t items, const float* coeffs, co
 
 int wam_quantize_normalize(int64_t images, int channels, int64_t plane, const float* rec, const float* mean,
                            const float* std, float* out, void* stream) {
-  if (images < 0 || channels < 1 || channels > 4 || plane < 1 || !rec || !mean || !std || !out)
-    return WAM_ERR_INVALID_ARG;
-  if (images == 0) return WAM_OK;
-  ChanNorm cn{};
-  for (int c = 0; c < channels; ++c) {
-    cn.mean[c] = mean[c];
-    cn.std[c] = std[c];
-  }
-  WamTimer tm((hipStream_t)stream, "k_quantize_normalize", 8.0 * images * channels * plane);
-  hipLaunchKernelGGL(k_quantize_normalize, dim3((unsigned)images), dim3(1024), 0, (hipStream_t)stream, channels, plane,
-                     rec, cn, out);
-  WAM_LAUNCH_CHECK();
-  return WAM_OK;
+  if (!mean || !std || !out) return WAM_ERR_INVALID_ARG;
+  return wam_quantize_normalize_ex(images, channels, plane, rec, 0, mean, std, nullptr, out, stream);
 }
 
 int wam_quantize_resize_normalize(int64_t images, int channels, int in_h, int in_w, const float* rec, int out_h,
                                   int out_w, int ksize_h, const int32_t* bounds_h, const int32_t* kk_h, int ksize_v,
                                   const int32_t* bounds_v, const int32_t* kk_v, int y0, int tmp_h, const float* mean,
                                   const float* std, uint8_t* scratch, float* out, void* stream) {
-  if (images < 0 || channels < 1 || channels > 4 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || !rec ||
-      !mean || !std || !scratch || !out)
-    return WAM_ERR_INVALID_ARG;
-  const bool horiz = bounds_h != nullptr, vert = bounds_v != nullptr;
-  if ((horiz && (!kk_h || ksize_h < 1)) || (vert && (!kk_v || ksize_v < 1))) return WAM_ERR_INVALID_ARG;
-  if (!horiz && out_w != in_w) return WAM_ERR_SHAPE;
-  if (!vert && out_h != in_h) return WAM_ERR_SHAPE;
-  if (horiz && (y0 < 0 || tmp_h < 1 || y0 + tmp_h > in_h)) return WAM_ERR_SHAPE;
-  if (images == 0) return WAM_OK;
-  ChanNorm cn{};
-  for (int c = 0; c < channels; ++c) {
-    cn.mean[c] = mean[c];
-    cn.std[c] = std[c];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t planes = images * channels;
-  const int64_t in_px = planes * (int64_t)in_h * in_w;
-  uint8_t* u8 = scratch;                 // planes x in_h x in_w
-  uint8_t* tmp = scratch + in_px;        // planes x tmp_h x out_w (horizontal pass)
-  {
-    WamTimer tm(st, "k_quantize_u8", 5.0 * in_px);
-    hipLaunchKernelGGL(k_quantize_u8, dim3((unsigned)images), dim3(1024), 0, st, channels, (int64_t)in_h * in_w, rec,
-                       u8);
-    WAM_LAUNCH_CHECK();
-  }
-  const uint8_t* vsrc = u8;
-  int vh = in_h;
-  if (horiz) {
-    const int64_t work = planes * (int64_t)tmp_h * out_w;
-    WamTimer tm(st, "k_pil_resize_h", (double)planes * tmp_h * in_w + (double)work);
-    hipLaunchKernelGGL(k_pil_resize_h, dim3(wam_grid(work, 256)), dim3(256), 0, st, planes, in_h, in_w, y0, tmp_h,
-                       out_w, ksize_h, bounds_h, kk_h, u8, tmp);
-    WAM_LAUNCH_CHECK();
-    vsrc = tmp;
-    vh = tmp_h;
-  }
-  const int64_t work = planes * (int64_t)out_h * out_w;
-  WamTimer tm(st, "k_pil_resize_v_norm", (double)planes * vh * out_w + 4.0 * work);
-  hipLaunchKernelGGL(k_pil_resize_v_norm, dim3(wam_grid(work, 256)), dim3(256), 0, st, images, channels, vh, out_h,
-                     out_w, (int)vert, ksize_v, bounds_v, kk_v, vsrc, cn, out);
-  WAM_LAUNCH_CHECK();
-  return WAM_OK;
+  return wam_quantize_resize_normalize_ex(images, channels, in_h, in_w, rec, 0, out_h, out_w, ksize_h, bounds_h, kk_h,
+                                          ksize_v, bounds_v, kk_v, y0, tmp_h, mean, std, scratch, out, stream);
 }
 
 int wam_gaussian_filter2d(int64_t items, int h, int w, const double* weights, int radius, const double* in,

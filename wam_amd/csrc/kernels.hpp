@@ -90,6 +90,19 @@ int launch_dwt2_synthesis_fused(const wam_plan* p, int64_t batch, int level, con
 
 #include "timing.hpp"
 
+// torchvision Normalize constants of up to 4 channels, passed to the quantisation (analyze2d.hip) and
+// resample (evaluate.hip) kernels by value
+struct ChanNorm {
+  float mean[4], std[4];
+};
+
+// Pillow's 8-bit BILINEAR resample + ToTensor / Normalize on quantised bytes (evaluate.hip), shared
+// by wam_quantize_resize_normalize_ex (analyze2d.hip)
+int launch_pil_resize_norm(int64_t images, int channels, int in_h, int in_w, int out_h, int out_w, int ksize_h,
+                           const int32_t* bounds_h, const int32_t* kk_h, int ksize_v, const int32_t* bounds_v,
+                           const int32_t* kk_v, int y0, int tmp_h, const float* mean, const float* std,
+                           uint8_t* scratch, float* out, hipStream_t st);
+
 // row-resident fused 2D kernels (dwt2_rows.hip): whole source rows staged in wave-private LDS
 bool dwt2_rows_supported(const wam_plan* p, int level, bool adjoint);
 int launch_dwt2_analysis_rows(const wam_plan* p, int64_t batch, const float* in, const int64_t* in_dims,

@@ -135,6 +135,62 @@ def pil_bilinear_coeffs(in_size, out_size):
     return ksize, bounds, fixed
 
 
+def show_images(x, dev):
+    """show(x[i]) (src/helpers.py:421-448) on the device: a list of [3, H, W] float32 tensors, min-max
+    normalised per image when outside [0, 1] (numpy: img -= min; img /= max)."""
+    xd = torch.as_tensor(x).detach().to(dev, torch.float32).contiguous()
+    out = []
+    for i in range(xd.shape[0]):
+        img = xd[i]
+        mn, mx = img.min(), img.max()
+        if bool(mx > 1) or bool(mn < 0):
+            img = img - mn
+            img = img / img.max()
+        out.append(img)
+    return out
+
+
+def array_layout(plan, dev):
+    """coeff_array_layout of a plan as (int32 positions on `dev`, array shape), cached."""
+    key = (plan, dev)
+    if key not in _LAYOUT:
+        pos, shape = coeff_array_layout(plan)
+        _LAYOUT[key] = (torch.as_tensor(pos.astype(np.int32)).to(dev), shape)
+    return _LAYOUT[key]
+
+
+def resize_default(dev, rec, M, C, rh, rw, mean, std, size=(224, 224), rule=0):
+    """The default transform on a reconstruction of another size: uint8 quantisation (rule 0: min-max,
+    rule 1: the analyzer's), Pillow's BILINEAR resample to 224 x 224 (what torchvision's Resize does to
+    the reference's PIL image) and ToTensor + Normalize, on the device
+    (wam_quantize_resize_normalize_ex). Returns (model inputs, the quantised bytes [M, C, rh * rw])."""
+    oh, ow = size
+    th = tv = None
+    if ow != rw:
+        th = pil_bilinear_coeffs(rw, ow)
+    if oh != rh:
+        tv = pil_bilinear_coeffs(rh, oh)
+    y0, tmp_h = 0, rh
+    if th is not None and tv is not None:  # the horizontal pass covers the rows the vertical one reads
+        b = tv[1]
+        y0, tmp_h = int(b[0, 0]), int(b[-1, 0] + b[-1, 1] - b[0, 0])
+        tv = (tv[0], b - np.array([y0, 0], dtype=b.dtype), tv[2])
+    dv = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+    bh = kh = bv = kv = None
+    if th is not None:
+        bh, kh = dv(th[1]), dv(th[2])
+    if tv is not None:
+        bv, kv = dv(tv[1]), dv(tv[2])
+    scratch = torch.empty(M * C * (rh * rw + (tmp_h * ow if th is not None else 0)) + 16, dtype=torch.uint8,
+                          device=dev)
+    out = torch.empty((M, C, oh, ow), dtype=torch.float32, device=dev)
+    p_ = lambda t: None if t is None else ptr(t)  # noqa: E731
+    check(lib.wam_quantize_resize_normalize_ex(M, C, rh, rw, ptr(rec), rule, oh, ow, th[0] if th else 0, p_(bh),
+                                               p_(kh), tv[0] if tv else 0, p_(bv), p_(kv), y0, tmp_h, mean, std,
+                                               ptr(scratch), ptr(out), stream_of(dev)))
+    return out, scratch[:M * C * rh * rw].view(M, C, rh * rw)
+
+
 class Eval2DWAM(WaveletAttribution2D):
     """src/evaluators.py:553-801 -- insertion / deletion (Petsiuk et al.), mu-fidelity (Bhatt et al.)."""
 
@@ -158,25 +214,10 @@ class Eval2DWAM(WaveletAttribution2D):
 
     # -------------------------------------------------------------------- device pipeline
     def _images(self, x):
-        """show(x[i]) (src/helpers.py:421-448) on the device: [N, 3, H, W] float32, min-max
-        normalised per image when outside [0, 1] (numpy: img -= min; img /= max)."""
-        xd = torch.as_tensor(x).detach().to(self._dev, torch.float32).contiguous()
-        out = []
-        for i in range(xd.shape[0]):
-            img = xd[i]
-            mn, mx = img.min(), img.max()
-            if bool(mx > 1) or bool(mn < 0):
-                img = img - mn
-                img = img / img.max()
-            out.append(img)
-        return out
+        return show_images(x, self._dev)
 
     def _layout(self, plan):
-        key = (plan, self._dev)
-        if key not in _LAYOUT:
-            pos, shape = coeff_array_layout(plan)
-            _LAYOUT[key] = (torch.as_tensor(pos.astype(np.int32)).to(self._dev), shape)
-        return _LAYOUT[key]
+        return array_layout(plan, self._dev)
 
     def _altered_inputs(self, img, masks):
         """masks [M, AH, AW] float32 device -> model inputs [M, 3, 224, 224] (or uint8 HWC numpy
@@ -206,35 +247,7 @@ class Eval2DWAM(WaveletAttribution2D):
         return self._resize_default(rec, M, C, rh, rw, mean, std)
 
     def _resize_default(self, rec, M, C, rh, rw, mean, std, size=(224, 224)):
-        """The default transform on a reconstruction of another size: uint8 quantisation, Pillow's
-        BILINEAR resample to 224 x 224 (what torchvision's Resize does to the reference's PIL image)
-        and ToTensor + Normalize, on the device (wam_quantize_resize_normalize)."""
-        dev = self._dev
-        oh, ow = size
-        th = tv = None
-        if ow != rw:
-            th = pil_bilinear_coeffs(rw, ow)
-        if oh != rh:
-            tv = pil_bilinear_coeffs(rh, oh)
-        y0, tmp_h = 0, rh
-        if th is not None and tv is not None:  # the horizontal pass covers the rows the vertical one reads
-            b = tv[1]
-            y0, tmp_h = int(b[0, 0]), int(b[-1, 0] + b[-1, 1] - b[0, 0])
-            tv = (tv[0], b - np.array([y0, 0], dtype=b.dtype), tv[2])
-        dv = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
-        bh = kh = bv = kv = None
-        if th is not None:
-            bh, kh = dv(th[1]), dv(th[2])
-        if tv is not None:
-            bv, kv = dv(tv[1]), dv(tv[2])
-        scratch = torch.empty(M * C * (rh * rw + (tmp_h * ow if th is not None else 0)) + 16, dtype=torch.uint8,
-                              device=dev)
-        out = torch.empty((M, C, oh, ow), dtype=torch.float32, device=dev)
-        p_ = lambda t: None if t is None else ptr(t)  # noqa: E731
-        check(lib.wam_quantize_resize_normalize(M, C, rh, rw, ptr(rec), oh, ow, th[0] if th else 0, p_(bh), p_(kh),
-                                                tv[0] if tv else 0, p_(bv), p_(kv), y0, tmp_h, mean, std,
-                                                ptr(scratch), ptr(out), stream_of(dev)))
-        return out
+        return resize_default(self._dev, rec, M, C, rh, rw, mean, std, size)[0]
 
     def _host_transform(self, rec):
         """The reference's PIL images (uint8 HWC -> PIL.Image.fromarray, src/evaluation_helpers.py

@@ -501,6 +501,31 @@ int wam_ew_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, i
 int wam_ew_maxpool_nhwc_backward(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride,
                                  int pad, const void* gy, const void* idx, int relu, void* gx, void* stream);
 
+/* Weight-stationary expanding pointwise GEMM with the neighbouring elementwise pass as its
+ * epilogue (wam_amd/csrc/model_pw.hip): out[M, N] = epilogue(x[M, K] . w[N, K]^T), x / out row-major
+ * (NHWC activations viewed as [N*H*W, C]), w the 1x1 convolution's weight as stored, fp32
+ * accumulation, one round-to-nearest-even store. Applied to the unrounded accumulator acc:
+ *   WAM_PW_TAIL: out = max((acc + bias_a[n]) + (r0[m, n] + bias_b[n]), 0)   r0 = s [M, N], r1 = NULL;
+ *                either bias may be NULL (k_add_bias_relu on the accumulator)
+ *   WAM_PW_MASK: out = r1[m, n] > 0 ? acc (+ r0[m, n]) : 0                  r1 = y [M, N], r0 = g2 [M, N]
+ *                or NULL; biases NULL (k_relu_mask on the accumulator; 0 where y is -0.0 or NaN)
+ * mode | WAM_PW_ROUNDED: acc is rounded to bf16 (nearest even) before the epilogue, i.e. the epilogue
+ * sees the value a bf16 GEMM followed by wam_ew_add_bias_relu / wam_ew_relu_mask sees; results then
+ * equal that pair's wherever the two fp32 accumulation orders round to the same bf16 value.
+ * wam_pw_supported: 1 for bf16 with (K, N) = (64, 256) or (128, 512), else 0. wam_pw_gemm returns
+ * WAM_ERR_UNSUPPORTED (out untouched) for another dtype or (K, N) or when x, w, r0, r1 or out is not
+ * 16-byte aligned, WAM_ERR_INVALID_ARG for M <= 0, a NULL x / w / out, an unknown mode or dtype, or
+ * operands the mode does not take. out must not alias an input. wam_pw_gemm_ex caps the persistent
+ * grid at max_workgroups per N split (0: the resident count), so that a test can make every
+ * workgroup loop over several tiles of a small M. */
+enum wam_pw_mode { WAM_PW_TAIL = 0, WAM_PW_MASK = 1, WAM_PW_ROUNDED = 16 };
+int wam_pw_supported(int dtype, int64_t K, int64_t N);
+int wam_pw_gemm(int mode, int dtype, int64_t M, int64_t K, int64_t N, const void* x, const void* w,
+                const void* bias_a, const void* bias_b, const void* r0, const void* r1, void* out, void* stream);
+int wam_pw_gemm_ex(int mode, int64_t M, int64_t K, int64_t N, const void* x, const void* w, const void* bias_a,
+                   const void* bias_b, const void* r0, const void* r1, void* out, int max_workgroups,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,10 @@ rewrites the traced graph so each chain is one HIP kernel (wam_amd/csrc/model_ew
 * ``relu(a + s)`` where a / s are biased convolutions (bottleneck tail, downsample shortcut)
   -> the convolutions without bias and ``AddBiasReLU``: out = max((a + b_a) + (s + b_s), 0) in
   one pass; backward = one ReLU-mask pass whose result feeds both branches.
+* where the tail's convolution is a pointwise one at a shape the in-tree GEMM serves (bf16, 64 ->
+  256 and 128 -> 512 channels: csrc/model_pw.hip), the GEMM and the tail are ONE launch (the
+  ``ConvNoBias`` defers to its ``AddBiasReLU``), and in a skip-linked identity block conv1's
+  input-gradient GEMM carries the producer's ReLU mask and the parked skip gradient as its epilogue.
 * the polyphase input convolution (``model_opt.InputConv2d``) followed by a ReLU gets the same
   bias + ReLU epilogue and a masked polyphase backward.
 
@@ -167,6 +171,47 @@ def _addmm_relu(b, x2, w2t):
         return torch.relu_(torch.addmm(b, x2, w2t))
 
 
+# ---- the expanding pointwise GEMM with its elementwise neighbour as the epilogue (csrc/model_pw.hip)
+_PW_TAIL, _PW_MASK = 0, 1
+# the model's launches round the accumulator to bf16 before the epilogue: the fused launch then
+# computes what torch.mm followed by the wam_ew_* pass computes (the c2 maps of the two-kernel path bit
+# for bit, profiles/r07b_dump_compare.log); applied to the unrounded accumulator the random-init bf16
+# ResNet-50's ReLU masks flip and the maps move by 8e-2 relative L2
+_PW_ROUNDED = 16
+# (mode, K, N) served by the fused kernel: the pairs that beat torch.mm + the wam_ew_* pass on
+# MI355X (scripts/kbench_pointwise.py); anything else stays on the two-kernel path
+_PW_ROUTES = {(_PW_TAIL, 64, 256), (_PW_TAIL, 128, 512), (_PW_MASK, 64, 256), (_PW_MASK, 128, 512)}
+
+
+def _pw_routed(mode, w2):
+    n, k = w2.shape
+    return (mode, k, n) in _PW_ROUTES and w2.is_contiguous() and bool(_lib.lib.wam_pw_supported(_DT[w2.dtype], k, n))
+
+
+def pw_gemm(mode, x2, w2, ba=None, bs=None, r0=None, r1=None):
+    """epilogue(x2 [M, K] @ w2 [N, K]^T) -> [M, N]; PW_TAIL: r0 = s, PW_MASK: r0 = g2 or None, r1 = y."""
+    m, k = x2.shape
+    n = w2.shape[0]
+    out = torch.empty((m, n), dtype=x2.dtype, device=x2.device)
+    cast = (lambda b: None if b is None else b.to(x2.dtype).contiguous())
+    _lib.check(_lib.lib.wam_pw_gemm(mode | _PW_ROUNDED, _dt(x2), m, k, n, _lib.ptr(x2), _lib.ptr(w2), _lib.ptr(cast(ba)),
+                                    _lib.ptr(cast(bs)), _lib.ptr(r0), _lib.ptr(r1), _lib.ptr(out), _stream(x2)))
+    return out
+
+
+class _PendingPW:
+    """A ConvNoBias GEMM handed to the AddBiasReLU that consumes it, which runs it with the residual
+    tail as its epilogue (one launch); any other consumer materialises it with today's mm."""
+
+    __slots__ = ("x", "x2", "w2")
+
+    def __init__(self, x, x2, w2):
+        self.x, self.x2, self.w2 = x, x2, w2
+
+    def materialize(self):
+        return _PointwiseConvFn.apply(self.x2.detach(), self.x, self.w2)
+
+
 class _SkipGrad:
     """Hand-off of a residual block's skip-path gradient to the block that produced its input.
 
@@ -176,14 +221,21 @@ class _SkipGrad:
     receives x detached and parks its skip gradient here, and the producer's backward, which
     autograd runs later (it is upstream of both users), applies its mask to the sum in one kernel
     (relu_mask(g, y, g2)). One box per forward call: the producer's forward opens it and the
-    consumer's forward takes it, so repeated forwards before a backward stay separate. Measured:
-    adding the skip gradient as the C operand of conv1's input-gradient GEMM instead gains nothing
-    (torch.addmm copies C into the output first; scripts/skip_ab.py)."""
+    consumer's forward takes it, so repeated forwards before a backward stay separate.
 
-    __slots__ = ("g",)
+    Where the consumer block's conv1 runs on the GEMM path at a routed shape, its input-gradient
+    GEMM takes the parked gradient and the producer's mask as its epilogue (PW_MASK: one launch
+    instead of mm + relu_mask, 0.67-0.68x the pair's time at the c2 shapes) and
+    marks the box `final`; the producer's backward then passes that gradient on as it is. `armed`
+    says the consumer add took the box, i.e. a skip gradient will be parked. torch.addmm cannot
+    do this: it copies its C operand into the output first (scripts/skip_ab.py)."""
+
+    __slots__ = ("g", "armed", "final")
 
     def __init__(self):
         self.g = None
+        self.armed = False
+        self.final = False
 
 
 class _SkipLink:
@@ -194,15 +246,34 @@ class _SkipLink:
         self.cur = None
 
 
+def _masked_sum(take, g, out):
+    """The producer's ReLU mask over g + the parked skip gradient -- or g as it is when the consumer's
+    conv1 backward already applied both (PW_MASK) and marked the box final."""
+    g2 = None
+    if take is not None:
+        if take.final:
+            take.final = False
+            return _like(g, out)
+        g2, take.g = take.g, None
+    return relu_mask(g, out, g2)
+
+
 class _ConvBiasReLUFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, geom):
+    def forward(ctx, x, w, b, geom, box=None, wt=None):
         x2 = _rows(x) if _pointwise(w, geom) else None
         ctx.gemm = x2 is not None
+        ctx.box = None
         if ctx.gemm:
             w2 = w.reshape(w.shape[0], w.shape[1])
             y = _unrows(_addmm_relu(b.to(x.dtype), x2, w2.t()), x)
-            ctx.save_for_backward(w2, y)
+            if box is not None and wt is not None and x.dtype == w.dtype:
+                # x is the linked producer's output: its mask and the skip gradient parked in the
+                # box become the epilogue of this convolution's input-gradient GEMM
+                ctx.box = box
+                ctx.save_for_backward(w2, y, wt, x)
+            else:
+                ctx.save_for_backward(w2, y)
             return y
         y = bias_act_(_conv_nd(x, w, *geom), b, True)
         ctx.save_for_backward(x, w, y)
@@ -212,11 +283,24 @@ class _ConvBiasReLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if ctx.gemm:
-            w2, y = ctx.saved_tensors
+            w2, y = ctx.saved_tensors[:2]
             gm = relu_mask(g, y)
-            return _unrows(torch.mm(_rows(gm), w2), y), None, None, None
+            box = ctx.box
+            if box is not None and box.armed:
+                wt, x = ctx.saved_tensors[2:]
+                # the consumer's tail runs before this backward (_link_skip_gradients), so its skip
+                # gradient is parked by now; a missing one would silently drop a gradient branch
+                if box.g is None:
+                    raise RuntimeError("wam_amd: the skip gradient of a linked residual block was not parked "
+                                       "before its conv1 backward")
+                g2 = _rows(box.g)
+                if g2 is not None and g2.dtype == gm.dtype:
+                    box.g, box.final = None, True
+                    dx = pw_gemm(_PW_MASK, _rows(gm), wt, None, None, g2, _rows(x))
+                    return _unrows(dx, x), None, None, None, None, None
+            return _unrows(torch.mm(_rows(gm), w2), y), None, None, None, None, None
         x, w, y = ctx.saved_tensors
-        return _conv_grad_input(relu_mask(g, y), x, w, *ctx.geom), None, None, None
+        return _conv_grad_input(relu_mask(g, y), x, w, *ctx.geom), None, None, None, None, None
 
 
 class _PointwiseConvFn(torch.autograd.Function):
@@ -252,14 +336,33 @@ class _AddBiasReLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
-        g2 = None
-        if ctx.take is not None:  # skip gradient of the consumer block, summed under the mask
-            g2, ctx.take.g = ctx.take.g, None
-        gm = relu_mask(g, out, g2)
+        gm = _masked_sum(ctx.take, g, out)  # skip gradient of the consumer block, summed under the mask
         if ctx.park is not None:  # s was passed detached: its gradient goes to s's producer
             ctx.park.g = gm
             return gm, None, None, None, None, None
         return gm, None, gm, None, None, None
+
+
+class _PWTailFn(torch.autograd.Function):
+    """relu((conv1x1(x, w2) + ba) + (s + bs)) in one launch. Backward = _AddBiasReLUFn's mask pass,
+    then _PointwiseConvFn's input-gradient GEMM for the convolution branch."""
+
+    @staticmethod
+    def forward(ctx, x, w2, ba, s, bs, park=None, take=None):
+        out = _unrows(pw_gemm(_PW_TAIL, _rows(x), w2, ba, bs, _rows(s)), s)
+        ctx.save_for_backward(w2, out)
+        ctx.park, ctx.take = park, take
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        w2, out = ctx.saved_tensors
+        gm = _masked_sum(ctx.take, g, out)
+        dx = _unrows(torch.mm(_rows(gm), w2), out)
+        if ctx.park is not None:
+            ctx.park.g = gm
+            return dx, None, None, None, None, None, None
+        return dx, None, None, gm, None, None, None
 
 
 class _PolyphaseReLUFn(torch.autograd.Function):
@@ -335,10 +438,26 @@ class ConvBiasReLU(nn.Module):
         b = conv.bias.detach().clone() if conv.bias is not None else torch.zeros(conv.out_channels)
         self.bias = nn.Parameter(b, requires_grad=False)
         self.geom = _geom(conv)
+        self.link_src = None  # _SkipLink: the input is a linked producer's output (fused mask backward)
+        self._wt = self._wt_key = None
 
+    def _weight_t(self):
+        """[C_in, C_out] copy of the frozen pointwise weight (PW_MASK's w operand), made once."""
+        w = self.weight
+        key = (w.data_ptr(), w.dtype, w.device, w._version)
+        if self._wt_key != key:
+            self._wt, self._wt_key = w.reshape(w.shape[0], w.shape[1]).t().contiguous(), key
+        return self._wt
 
     def forward(self, x):
-        return _ConvBiasReLUFn.apply(x, self.weight, self.bias, self.geom)
+        box = wt = None
+        if self.link_src is not None and self.link_src.cur is not None and torch.is_grad_enabled() and x.is_cuda \
+                and _pointwise(self.weight, self.geom) and x.dtype == self.weight.dtype \
+                and (_PW_MASK, self.weight.shape[0], self.weight.shape[1]) in _PW_ROUTES:
+            wt = self._weight_t()
+            if _pw_routed(_PW_MASK, wt):
+                box = self.link_src.cur
+        return _ConvBiasReLUFn.apply(x, self.weight, self.bias, self.geom, box, wt)
 
 
 class ConvNoBias(nn.Module):
@@ -348,12 +467,15 @@ class ConvNoBias(nn.Module):
         super().__init__()
         self.weight = nn.Parameter(conv.weight.detach().clone(), requires_grad=False)
         self.geom = _geom(conv)
+        self.defer = False  # its only user is an AddBiasReLU's `a` operand, which can run the GEMM itself
 
     def forward(self, x):
         if _pointwise(self.weight, self.geom):
             x2 = _rows(x)
             if x2 is not None:
                 w2 = self.weight.reshape(self.weight.shape[0], self.weight.shape[1])
+                if self.defer and x.dtype == w2.dtype and _pw_routed(_PW_TAIL, w2):
+                    return _PendingPW(x, x2, w2)
                 return _PointwiseConvFn.apply(x2.detach(), x, w2)
         return _conv_nd(x, self.weight, *self.geom)
 
@@ -379,8 +501,25 @@ class AddBiasReLU(nn.Module):
                 return False
         return True
 
+    def _pending_ok(self, p, s):
+        """The fused GEMM writes [M, N] rows next to s's rows: s dense channels_last of the output's shape."""
+        x = p.x
+        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.device == x.device and s.dtype == x.dtype
+                and tuple(s.shape) == (x.shape[0], p.w2.shape[0], x.shape[2], x.shape[3]) and _rows(s) is not None):
+            return False
+        for b in (self.bias_a, self.bias_s):
+            if b is not None and (b.dim() != 1 or b.numel() != s.shape[1]):
+                return False
+        return True
+
     def forward(self, a, s):
-        if not self._fusable(a, s):
+        pending = None
+        if isinstance(a, _PendingPW):
+            if self._pending_ok(a, s):
+                pending, a = a, a.x
+            else:
+                a = a.materialize()
+        if pending is None and not self._fusable(a, s):
             # broadcast / mixed operands (e.g. relu(x + pos_embed)): plain torch, no skip hand-off
             if self.link_out is not None:
                 self.link_out.cur = None
@@ -391,10 +530,13 @@ class AddBiasReLU(nn.Module):
         park = take = None
         if self.link_in is not None and self.link_in.cur is not None and torch.is_grad_enabled():
             park, self.link_in.cur = self.link_in.cur, None
+            park.armed = True
             s = s.detach()
         if self.link_out is not None:
             grad = torch.is_grad_enabled() and (a.requires_grad or s.requires_grad)
             take = self.link_out.cur = _SkipGrad() if grad else None
+        if pending is not None:
+            return _PWTailFn.apply(a, pending.w2, self.bias_a, s, self.bias_s, park, take)
         return _AddBiasReLUFn.apply(a, self.bias_a, s, self.bias_s, park, take)
 
 
@@ -520,6 +662,7 @@ def fuse_elementwise(gm):
                 c = _fusable_conv(a, mods)
                 if c is not None and c.bias is not None:
                     cname = add_mod(a.target, ConvNoBias(c))
+                    mods[cname].defer = a is src.args[0]
                     with g.inserting_before(a):
                         na = g.call_module(cname, (a.args[0],))
                     operands.append(na)
@@ -594,5 +737,7 @@ def _link_skip_gradients(gm, mods):
         link = _SkipLink()
         mods[node.target].link_out = link
         mods[add[0].target].link_in = link
+        if type(mods.get(other[0].target)) is ConvBiasReLU and other[0].args[0] is node:
+            mods[other[0].target].link_src = link  # the block's conv1: fused mask backward
         links += 1
     return links

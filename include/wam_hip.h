@@ -442,6 +442,67 @@ int wam_quantize_resize_normalize_ex(int64_t images, int channels, int in_h, int
                                      const float* mean, const float* std, uint8_t* scratch, float* out,
                                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pixel-domain baselines (EvalImageBaselines, src/evaluators.py:805-1180; GradCAM, GradCAMPlusPlus,
+ * SmoothGrad, src/evaluation_helpers.py:72-320). The reference's per-image, per-mask CPU loop
+ * (generate_masks -> masks[i, :, :, None] * img -> normalize_data -> uint8 -> PIL -> transform) and its
+ * per-channel Grad-CAM loop become one ranking-to-model-input pass, one superpixel-to-model-input pass
+ * and one workgroup per CAM. The masks themselves are never stored.
+ * The two mask entries share their outputs. For masked image i (channels <= 4 planes of `plane`
+ * floats, v[c, p] below), with mn / mx the minimum / maximum of v over all channels of the image:
+ *   masked (float32): v itself;
+ *   u8: q = rule 0 of wam_quantize_normalize_ex on v (s = ((v - mn) / (mx - mn)) * 255, every operation
+ *       an IEEE float32 one in that order; q = 0 when s is NaN -- the image whose pixels are all equal --
+ *       else s truncated);
+ *   out (float32): (q / 255 - mean[c]) / std[c], bit-identical to wam_quantize_normalize_ex(rule 0) applied
+ *       to `masked`; mean / std are HOST arrays of `channels` values (needed only with out).
+ * Each is laid out [images, channels, plane], may be NULL, and at least one is not. Inputs are finite.
+ * ---------------------------------------------------------------------------------------------- */
+/* Ranking to the model inputs of insertion / deletion. img [sets, channels, plane] float32; rank
+ * [sets, plane] int32 (device): rank[s, p] = the position of pixel p of set s in the descending
+ * importance order, in [0, plane). The selection rule is the one of the two rank-mask entries above
+ * with rank_len = plane: thr(0) = 0, thr(m) = min(m * n_comp, plane) for 0 < m < n_iter, thr(n_iter) =
+ * plane; mask m keeps pixel p when (rank[s, p] < thr(m)) != (deletion != 0). Image (s, m) =
+ * s * (n_iter + 1) + m has v[c, p] = img[s, c, p] * (keep ? 1.0f : 0.0f) (a dropped negative pixel is
+ * -0.0f). ws (device, 4-byte aligned): wam_rank_mask_pixels_ws_bytes(sets, n_iter) = 8 * sets *
+ * ((n_iter + 1) + 32 * (n_iter + 2)) bytes, written by the call and needing no initialisation (the
+ * extrema of every image, found from one pass over each set -- a pixel enters the kept set at one mask
+ * and stays --, and the tables of the up to 32 workgroups that share that pass). sets <= 65535,
+ * n_iter >= 1, n_comp >= 0; n_iter > 4096: WAM_ERR_UNSUPPORTED (a workgroup's extrema table is held
+ * in LDS). 16-byte stores when plane % 4 == 0
+ * and img, rank, masked and out are 16-byte (u8: 4-byte) aligned, scalar ones otherwise; the values are
+ * the same. */
+int64_t wam_rank_mask_pixels_ws_bytes(int64_t sets, int64_t n_iter);
+int wam_rank_mask_pixels(int64_t sets, int channels, int64_t plane, const float* img, const int32_t* rank,
+                         int64_t n_iter, int64_t n_comp, int deletion, const float* mean, const float* std,
+                         float* masked, uint8_t* u8, float* out, void* ws, void* stream);
+/* mu-fidelity's superpixel masks on one image. img [channels, plane] float32; grid [n_masks, grid_len]
+ * float32 (device); cell [plane] int32 (device): the grid cell of every pixel (scipy.ndimage.zoom,
+ * order 0, as for wam_upsample_masks). Image m has v[c, p] = grid[m, cell[p]] * img[c, p], one float32
+ * multiply; a cell outside [0, grid_len) multiplies by 0.0f. */
+int wam_cell_mask_pixels(int channels, int64_t plane, const float* img, int64_t n_masks, int64_t grid_len,
+                         const float* grid, const int32_t* cell, const float* mean, const float* std, float* masked,
+                         uint8_t* u8, float* out, void* stream);
+/* Grad-CAM (plus_plus == 0) and Grad-CAM++ as the reference computes them. act, grad [images, K, h, w]
+ * float32: the target layer's output and the gradient of the class score with respect to it. Per image:
+ *   w_k = mean over h x w of grad_k;  plus_plus != 0: w_k = sum(max(grad_k, 0) * act_k) / (sum(act_k) + 1e-8)
+ *   (the reference's formula, not the paper's);
+ *   cam = max(sum_k w_k * act_k, 0);  cam -= min(cam);  cam /= max(cam)  (IEEE division: a CAM that is
+ *   nowhere positive is 0 / 0, and the whole map is NaN, as in the reference);
+ *   out [images, out_h, out_w] float32 = torch's bilinear resize with align_corners=False: source
+ *   coordinate scale * (dst + 0.5) - 0.5 in float32 with scale = (float)in / out, clamped at 0.
+ * The sums, the normalisation and the interpolation are taken in float64 and rounded to float32 once
+ * (the reference accumulates K float32 planes in channel order). One workgroup per image; 8 * (K + h * w
+ * + 1040) bytes of LDS, WAM_ERR_UNSUPPORTED above 160 KiB. */
+int wam_cam_maps(int64_t images, int64_t K, int h, int w, const float* act, const float* grad, int plus_plus,
+                 int out_h, int out_w, float* out, void* stream);
+/* The channel mean the gradient methods end in. g [items, channels, plane] float32; t_c = g[n, c, p],
+ * times mult[n, c, p] when mult != NULL (same shape), then its absolute value when absolute != 0;
+ * m = ((t_0 + t_1) + ...) / channels in float32, sequential (numpy's order for a short axis).
+ * out_f32 [items, plane] = m and / or acc_f64 [items, plane] += (double)m; at least one is not NULL. */
+int wam_channel_mean(int64_t items, int channels, int64_t plane, const float* g, const float* mult, int absolute,
+                     float* out_f32, double* acc_f64, void* stream);
+
 /* WaveletAttribution3D.visualize (lib/wam_3D.py:662-719): cube [items, S, S, S]
  * float32 (the |grad| cube of smooth / IG) -> out [items, levels + 2, S, S, S] float32: per level
  * the block (approximation corner, or add + ada + add + daa + dad + dda of the detail shell, as

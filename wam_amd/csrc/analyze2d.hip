@@ -8,6 +8,7 @@
 // stored -- and one workgroup per reconstruction does the min / max reduction and the quantisation.
 // Both kernels are HBM-bound streaming passes.
 #include "kernels.hpp"
+#include "quantize.hpp"
 
 namespace {
 
@@ -126,47 +127,7 @@ __global__ void __launch_bounds__(256) k_threshold_mask(int64_t images, int chan
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- quantisation of a reconstruction, one workgroup per image (channels x plane floats): the min / max
-// pass, a barrier, then the map on a second read of the image
-__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
-  __shared__ float smn[16], smx[16];
-  for (int s = 32; s > 0; s >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, s, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    smn[w] = mn;
-    smx[w] = mx;
-  }
-  __syncthreads();
-  mn = smn[0];
-  mx = smx[0];
-  for (int i = 1; i < nw; ++i) {
-    mn = fminf(mn, smn[i]);
-    mx = fmaxf(mx, smx[i]);
-  }
-}
-
-// RULE 0: normalize_data (src/evaluation_helpers.py:433-435) -> (x * 255).astype(uint8): min-max,
-// values in [0, 255], truncation. A constant image (e.g. insertion step 0: all coefficients masked, a
-// zero reconstruction) gives 0 / 0 = NaN, which numpy's NaN -> uint8 cast turns into 0 on x86
-// (cvttss2si's 0x80000000, low byte 0): pinned here explicitly rather than left to the hardware's
-// float -> int conversion of NaN.
-// RULE 1: the analyzer's ((x - mn) / mx - mn) * 255 (src/analyzers.py:155; the precedence is the
-// reference's), every step a float32 round-to-nearest operation in numpy's order, then numpy's
-// float32 -> uint8 cast as x86 does it: truncation toward zero to int32, the low 8 bits kept (-3.7 ->
-// 253, 300.7 -> 44); NaN and values outside int32 give cvttss2si's 0x80000000, so 0. Pinned
-// explicitly too: the hardware's own conversion saturates.
-template <int RULE>
-__device__ __forceinline__ uint8_t quantize_one(float x, float mn, float mx) {
-  if (RULE == 0) {
-    const float s = __fmul_rn(__fdiv_rn(x - mn, mx - mn), 255.f);
-    return (s != s) ? (uint8_t)0 : (uint8_t)(int)s;
-  }
-  const float s = __fmul_rn(__fsub_rn(__fdiv_rn(__fsub_rn(x, mn), mx), mn), 255.f);
-  if (!(fabsf(s) < 2147483648.f)) return 0;  // NaN, +-inf, beyond int32
-  return (uint8_t)((int)s & 255);
-}
+// pass (block_minmax), a barrier, then the map (quantize_one, quantize.hpp) on a second read of the image
 
 // VEC: plane is a multiple of 4 and the buffers are 16-byte (u8: 4-byte) aligned, so a thread handles 4
 // consecutive values of one channel per step: a 16-byte load, a 4-byte and a 16-byte store. The values are

@@ -587,3 +587,12 @@ class Eval1DWAM(WaveletAttribution1D):
         components inserted (insertion with n_iter = 2, rows 1 and 2)."""
         preds = np.array(self.evaluate_auc(x, y, "insertion", target, 2, argmax=True))
         return np.argmax(preds[:, 1:, :], axis=2).tolist()
+
+
+def __getattr__(name):
+    """``EvalImageBaselines`` (the reference keeps it in the same module) lives in wam_amd.baselines,
+    which builds on this module."""
+    if name == "EvalImageBaselines":
+        from .baselines import EvalImageBaselines
+        return EvalImageBaselines
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

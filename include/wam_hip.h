@@ -105,6 +105,21 @@ int wam_waverec(const wam_plan* plan, int64_t batch, const float* coeffs, const 
 int wam_waverec_adjoint(const wam_plan* plan, int64_t batch, const float* grad, float* coeff_grads,
                         void* workspace, void* stream);
 
+/* Adjoint of wam_wavedec w.r.t. x (the backward pass of ptwt.wavedec*): coeff_grads band-major,
+ * batch items -> grad_x [batch, shape...]. Per axis of a level it is the transposed convolution of
+ * the band gradients with the analysis filters, its padded tails folded back onto the signal by the
+ * plan's boundary mode (every mode, any length; an odd length does not grow). Outputs are gathered
+ * in a fixed order, so two calls give the same bits. workspace: at least
+ * wam_wavedec_adjoint_workspace_bytes (never more than wam_plan_workspace_bytes). */
+int     wam_wavedec_adjoint(const wam_plan* plan, int64_t batch, const float* coeff_grads, float* grad_x,
+                            void* workspace, void* stream);
+int64_t wam_wavedec_adjoint_workspace_bytes(const wam_plan* plan, int64_t batch);
+/* which kernels serve a level of wam_wavedec_adjoint: 0 = axis (per-axis kernels, every plan),
+ * 1 = fold2d (2D, filter length <= 20, the level longer than the pad on both axes: streaming level
+ * synthesis for the interior plus a border kernel for the folded tails); level 0 = finest; works on
+ * host-only plans; negative on bad arguments */
+int     wam_plan_wavedec_adjoint_route(const wam_plan* plan, int level);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused WAM passes (2D, rows <= 512 samples, filter length in {2,4,6,8,12,16,20})
  * ---------------------------------------------------------------------------------------------- */

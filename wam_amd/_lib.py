@@ -44,6 +44,9 @@ _SIGS = {
     "wam_wavedec": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wam_waverec": (c_int, [c_vp, c_i64, c_vp, ctypes.POINTER(c_f32), c_int, c_vp, c_vp, c_vp]),
     "wam_waverec_adjoint": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wam_wavedec_adjoint": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wam_wavedec_adjoint_workspace_bytes": (c_i64, [c_vp, c_i64]),
+    "wam_plan_wavedec_adjoint_route": (c_int, [c_vp, c_int]),
     "wam_item_sigma": (c_int, [c_i64, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp]),
     "wam_item_sigma_ws_bytes": (c_i64, [c_i64, c_i64]),
     "wam_item_sigma_ws": (c_int, [c_i64, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp]),

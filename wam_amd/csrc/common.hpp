@@ -75,6 +75,7 @@ struct WamRoutes {
   WamMaps maps;                          // the fused adjoint + maps pass
   bool maps_coop;                        // the plane maps pass runs COOP: it takes bf16 gradients
   bool noise0;                           // level 0 of the analysis takes fused SmoothGrad noise
+  uint8_t dadj_level[WAM_MAX_LEVELS];    // adjoint of wavedec, per level: WAM_DADJ_AXIS / WAM_DADJ_FOLD2D
 };
 
 struct wam_plan {

@@ -253,3 +253,22 @@ int launch_dwt2_synthesis_fused(const wam_plan* p, int64_t batch, int level, con
   }
 #undef WAM_SYN_CASE
 }
+
+// The same streaming level synthesis with a caller-chosen filter set (fset, fset + 1: lo then hi)
+// and output dims (oh <= 2 mh - L + 2, ow likewise): the interior term of the wavedec adjoint
+// (dwt_adjoint.hip), which runs it with the analysis filters onto the level's input dims.
+int launch_dwt2_synthesis_fused_to(const wam_plan* p, int64_t batch, int level, const SynBatch& sb,
+                                   const float* const* sub, int fset, int oh, int ow, hipStream_t st) {
+  if (sb.na < 1 || sb.na > kSynMaxAlpha) return WAM_ERR_INVALID_ARG;
+  const float* filt = p->d_filt + fset * p->L;
+  int mh = (int)p->lout[level][0], mw = (int)p->lout[level][1];
+  if (oh < 1 || ow < 1 || oh > 2 * mh - p->L + 2 || ow > 2 * mw - p->L + 2) return WAM_ERR_INVALID_ARG;
+#define WAM_SYN_CASE(LL) \
+  case LL: return launch_syn_L<LL>(batch, sub[0], sub[1], sub[2], mh, mw, sb, oh, ow, p->pad, filt, st);
+  switch (p->L) {
+    WAM_SYN_CASE(2) WAM_SYN_CASE(4) WAM_SYN_CASE(6) WAM_SYN_CASE(8) WAM_SYN_CASE(10)
+    WAM_SYN_CASE(12) WAM_SYN_CASE(14) WAM_SYN_CASE(16) WAM_SYN_CASE(18) WAM_SYN_CASE(20)
+    default: return WAM_ERR_UNSUPPORTED;
+  }
+#undef WAM_SYN_CASE
+}

@@ -87,6 +87,20 @@ struct SynBatch {
 };
 int launch_dwt2_synthesis_fused(const wam_plan* p, int64_t batch, int level, const SynBatch& sb,
                                 const float* const* sub, hipStream_t st);
+// the same kernel with a caller-chosen filter set (fset: lo, fset + 1: hi) and output dims
+int launch_dwt2_synthesis_fused_to(const wam_plan* p, int64_t batch, int level, const SynBatch& sb,
+                                   const float* const* sub, int fset, int oh, int ow, hipStream_t st);
+
+// adjoint of the boundary-extended analysis (dwt_adjoint.hip): the backward pass of wam_wavedec
+enum { WAM_DADJ_AXIS = 0, WAM_DADJ_FOLD2D = 1 };
+bool dwt2_adjoint_fold_supported(const wam_plan* p, int level);
+// lo / hi: [outer, m, inner] gradients of the two analysis outputs -> gx [outer, n, inner]
+int launch_analysis_adjoint_axis(const float* lo, const float* hi, float* gx, int64_t outer, int m, int n,
+                                 int64_t inner, int padl, int mode, const float* flo, const float* fhi, int L,
+                                 hipStream_t st);
+// one 2D level: a (LL gradient) and sub (H, V, D gradients) [batch, mh, mw] -> out [batch, lin[level]]
+int launch_dwt2_adjoint_fold(const wam_plan* p, int64_t batch, int level, const float* a, const float* const* sub,
+                             float* out, hipStream_t st);
 
 #include "timing.hpp"
 

@@ -46,6 +46,8 @@ static void resolve_routes(wam_plan* p) {
   else if (dwt1_tile_supported(p, false)) r.syn = WAM_WHOLE_TILE1;
   else if (dwt3_haar_supported(p)) r.syn = WAM_WHOLE_HAAR3;
   r.syn_level = below_rows;
+  for (int l = 0; l < p->levels; ++l)
+    r.dadj_level[l] = dwt2_adjoint_fold_supported(p, l) ? WAM_DADJ_FOLD2D : WAM_DADJ_AXIS;
   r.maps = r.adj.whole == WAM_WHOLE_PLANE ? WAM_MAPS_PLANE : adj_rows_all ? WAM_MAPS_ROWS : WAM_MAPS_NONE;
   r.maps_coop = r.maps == WAM_MAPS_PLANE && dwt2_plane_maps_coop(p);
   // fused noise counts groups of 4 elements along the last axis; the kernels that take it are the
@@ -389,12 +391,15 @@ int generic_analysis_level(const wam_plan* p, int64_t batch, const float* in, co
 }
 
 // One synthesis level (c_pos order handled by the caller). a_in: approximation (band or previous
-// output), sub[k]: detail bands; out: cropped result.
+// output), sub[k]: detail bands; out: cropped result. dec_adjoint: the adjoint of the analysis level
+// instead (the same pairing of parts per axis; analysis filters, tails folded by the plan's mode,
+// output dims lin[level], scales unused).
 int generic_synthesis_level(const wam_plan* p, int64_t batch, int level, const float* a_in, float a_scale,
-                            const float* const* sub, float d_scale, float* out, float* tmp, hipStream_t st) {
+                            const float* const* sub, float d_scale, float* out, float* tmp, hipStream_t st,
+                            bool dec_adjoint = false) {
   int nd = p->ndim;
-  const float* rlo = p->d_filt + WAM_F_SYN_LO * p->L;
-  const float* rhi = p->d_filt + WAM_F_SYN_HI * p->L;
+  const float* rlo = p->d_filt + (dec_adjoint ? WAM_F_ANA_LO : WAM_F_SYN_LO) * p->L;
+  const float* rhi = p->d_filt + (dec_adjoint ? WAM_F_ANA_HI : WAM_F_SYN_HI) * p->L;
   struct Part { int key; const float* ptr; float scale; };
   Part cur[8];
   int ncur = 1 << nd;
@@ -411,7 +416,8 @@ int generic_synthesis_level(const wam_plan* p, int64_t batch, int level, const f
     int64_t inner = 1;
     for (int a = ax + 1; a < nd; ++a) inner *= dims[a];
     int m = (int)dims[ax];
-    int nout = (int)(2 * dims[ax] - 2 + p->L - 2 * p->pad - p->extra[level][ax]);
+    int nout = dec_adjoint ? (int)p->lin[level][ax]
+                           : (int)(2 * dims[ax] - 2 + p->L - 2 * p->pad - p->extra[level][ax]);
     int64_t odims[WAM_MAX_NDIM];
     for (int a = 0; a < nd; ++a) odims[a] = dims[a];
     odims[ax] = nout;
@@ -427,8 +433,10 @@ int generic_synthesis_level(const wam_plan* p, int64_t batch, int level, const f
         if (cur[j].key == (cur[i].key | bit)) pd = &cur[j];
       float* dst = (ax == 0) ? out : tcur;
       if (ax != 0) tcur += part_elems;
-      int rc = launch_synthesis_axis(pa->ptr, pd->ptr, dst, outer, m, nout, inner, p->pad, rlo, rhi, p->L,
-                                     pa->scale, pd->scale, st);
+      int rc = dec_adjoint ? launch_analysis_adjoint_axis(pa->ptr, pd->ptr, dst, outer, m, nout, inner, p->pad,
+                                                          p->mode, rlo, rhi, p->L, st)
+                           : launch_synthesis_axis(pa->ptr, pd->ptr, dst, outer, m, nout, inner, p->pad, rlo, rhi,
+                                                   p->L, pa->scale, pd->scale, st);
       if (rc) return rc;
       nxt[nn++] = {cur[i].key, dst, 1.0f};
     }
@@ -673,6 +681,46 @@ int wam_waverec(const wam_plan* p, int64_t batch, const float* coeffs, const flo
       a_cur = dst;
       a_scale = 1.0f;
     }
+  }
+  return WAM_OK;
+}
+
+// Backward of wam_wavedec: coarsest level first, each level turning the LL gradient (band 0, then
+// the previous level's result) and its detail gradients into an array of lin[l] -- the layout of the
+// per-level synthesis above, without the odd-length growth. The workspace holds the LL ping-pong and
+// the per-axis intermediates of the axis route.
+int64_t wam_wavedec_adjoint_workspace_bytes(const wam_plan* p, int64_t batch) {
+  if (!p || batch < 0) return -1;
+  return (2 * syn_ll_stride(p, batch) + generic_syn_tmp(p, batch) + 64) * (int64_t)sizeof(float);
+}
+
+int wam_plan_wavedec_adjoint_route(const wam_plan* p, int level) {
+  if (!p || level < 0 || level >= p->levels) return -WAM_ERR_INVALID_ARG;
+  return p->routes.dadj_level[level];
+}
+
+int wam_wavedec_adjoint(const wam_plan* p, int64_t batch, const float* coeff_grads, float* grad_x, void* ws,
+                        void* stream) {
+  if (!p || !p->d_filt || !coeff_grads || !grad_x || !ws || batch < 0) return WAM_ERR_INVALID_ARG;
+  if (batch == 0) return WAM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t ll = syn_ll_stride(p, batch);
+  float* w = (float*)ws;
+  float* abuf[2] = {w, w + ll};
+  float* tmp = w + 2 * ll;
+  const float* a_cur = coeff_grads;  // band 0 = the gradient of A_J
+  for (int c = 0; c < p->levels; ++c) {
+    const int l = p->levels - 1 - c;
+    float* sub[7];
+    band_ptrs(p, batch, (float*)coeff_grads, l, sub);
+    float* dst = l == 0 ? grad_x : abuf[c & 1];
+    // the streaming synthesis stores pixel pairs: a destination that is not 8-byte aligned (a
+    // property of the call, not of the plan) takes the per-axis kernels
+    const bool fold = p->routes.dadj_level[l] == WAM_DADJ_FOLD2D && ((uintptr_t)dst & 7) == 0;
+    const int rc = fold ? launch_dwt2_adjoint_fold(p, batch, l, a_cur, sub, dst, st)
+                        : generic_synthesis_level(p, batch, l, a_cur, 1.0f, sub, 1.0f, dst, tmp, st, true);
+    if (rc) return rc;
+    a_cur = dst;
   }
   return WAM_OK;
 }

@@ -135,6 +135,24 @@ class Plan:
         check(lib.wam_waverec_adjoint(self._h, batch, ptr(grad), ptr(out), ptr(ws), stream_of(grad.device)))
         return out
 
+    def wavedec_adjoint(self, coeff_grads_flat, batch, out=None):
+        """band-major coefficient gradients -> grad_x [batch, *shape] (wavedec's VJP)."""
+        require_cuda(coeff_grads_flat, "coefficient gradients")
+        flat = coeff_grads_flat.contiguous()
+        if flat.numel() != batch * self.coeff_numel:
+            raise ValueError("expected %d x %d coefficient gradients, got %d" % (batch, self.coeff_numel,
+                                                                                   flat.numel()))
+        if out is None:
+            out = torch.empty((batch,) + self.shape, dtype=torch.float32, device=flat.device)
+        ws = self.workspace(batch)  # never smaller than wam_wavedec_adjoint_workspace_bytes
+        check(lib.wam_wavedec_adjoint(self._h, batch, ptr(flat), ptr(out), ptr(ws), stream_of(flat.device)))
+        return out
+
+    @property
+    def wavedec_adjoint_routes(self):
+        """Per level, finest first: 'axis' or 'fold2d' (wam_plan_wavedec_adjoint_route)."""
+        return [("axis", "fold2d")[lib.wam_plan_wavedec_adjoint_route(self._h, l)] for l in range(self.levels)]
+
     # ---------------------------------------------------------------- fused WAM passes
     @property
     def caps(self):

@@ -6,8 +6,12 @@ lib/wam_1D.py:109,117,370, lib/wam_3D.py:194,206,222,620): same argument names, 
 folding, same output containers, same sizes (odd lengths reconstruct to n+1).
 ``waverec*`` are differentiable: their backward is the HIP adjoint kernel (zero-padded analysis
 with reverse(rec) filters), which is what the reference's ``loss.backward()`` computes through
-ptwt's conv_transpose. ``wavedec*`` produce constants (WAM turns them into leaves); asking for a
-gradient through them raises instead of silently returning a wrong one.
+ptwt's conv_transpose. ``wavedec*`` are differentiable too: when the analysed signal requires grad,
+their backward is the adjoint of the boundary-extended analysis (``Plan.wavedec_adjoint``: the
+transposed convolution with the analysis filters, padded tails folded back by the mode), as
+autograd through ptwt gives; otherwise they run the plain forward and return constants. Both
+backward passes are Functions whose own backward is the forward transform, so ``create_graph=True``
+works through either pair.
 Inputs must be float32 CUDA (HIP) tensors -- there is no CPU path.
 """
 import numpy as np
@@ -19,15 +23,36 @@ from .filters import get_wavelet
 from .plan import get_plan
 
 
-def _no_grad_input(x):
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise NotImplementedError("wam_amd.wavedec*: gradients w.r.t. the analysed signal are not implemented "
-                                  "(WAM differentiates w.r.t. the coefficients only)")
+class _WavedecFn(torch.autograd.Function):
+    """x [batch, *shape] -> flat coefficients; backward = the wavedec adjoint kernels."""
+
+    @staticmethod
+    def forward(ctx, plan, batch, x):
+        ctx.plan = plan
+        ctx.batch = batch
+        return plan.wavedec(x.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None, _WavedecAdjointFn.apply(ctx.plan, ctx.batch, g)
+
+
+class _WavedecAdjointFn(torch.autograd.Function):
+    """The adjoint is linear: its own backward is wavedec again (create_graph=True)."""
+
+    @staticmethod
+    def forward(ctx, plan, batch, g):
+        ctx.plan = plan
+        ctx.batch = batch
+        return plan.wavedec_adjoint(g.detach(), batch)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return None, None, _WavedecFn.apply(ctx.plan, ctx.batch, gg.contiguous())
 
 
 def _dec(data, wavelet, level, mode, ndim):
     require_cuda(data, "data")
-    _no_grad_input(data)
     shape = tuple(data.shape[-ndim:])
     lead = tuple(data.shape[:-ndim])
     batch = int(np.prod(lead)) if lead else 1
@@ -38,7 +63,10 @@ def _dec(data, wavelet, level, mode, ndim):
         while (n // 2 ** (level + 1)) >= L - 1:
             level += 1
     plan = get_plan(ndim, shape, level, wavelet, mode, data.device)
-    flat = plan.wavedec(data.detach().reshape((batch,) + shape))
+    if torch.is_grad_enabled() and data.requires_grad:
+        flat = _WavedecFn.apply(plan, batch, data.reshape((batch,) + shape))
+    else:
+        flat = plan.wavedec(data.detach().reshape((batch,) + shape))
     return plan, plan.split(flat, batch, lead)
 
 
@@ -51,7 +79,21 @@ class _WaverecFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return None, None, ctx.plan.adjoint(g.contiguous())
+        return None, None, _WaverecAdjointFn.apply(ctx.plan, ctx.batch, g)
+
+
+class _WaverecAdjointFn(torch.autograd.Function):
+    """plan.adjoint as a Function: linear, so its backward is waverec again (create_graph=True)."""
+
+    @staticmethod
+    def forward(ctx, plan, batch, g):
+        ctx.plan = plan
+        ctx.batch = batch
+        return plan.adjoint(g.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, gg):
+        return None, None, _WaverecFn.apply(ctx.plan, ctx.batch, gg.contiguous())
 
 
 def _rec(bands, wavelet, ndim):

@@ -210,7 +210,8 @@ def test_matlab_known_answers(wam):
                                               ("sym8", (96, 128), 2, "symmetric"), ("db6", (60, 44), 2, "constant"),
                                               ("haar", (512, 512), 5, "periodic"), ("db4", (37, 53), 2, "reflect"),
                                               ("sym4", (300, 700), 3, "symmetric"), ("db10", (33, 260), 1, "zero"),
-                                              ("coif1", (7, 9), 1, "periodic")])
+                                              ("coif1", (7, 9), 1, "periodic"), ("db5", (70, 90), 2, "reflect"),
+                                              ("db7", (100, 77), 2, "zero"), ("db9", (61, 95), 2, "constant")])
 def test_fused_2d_paths_agree(wam, wav, shape, J, mode):
     """The 2D analysis implementations (row-resident, column-strip, per-axis) agree: bit-exact
     between the fused kernels (same tap order), to fp32 rounding with the per-axis one."""

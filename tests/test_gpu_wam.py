@@ -65,12 +65,15 @@ def test_glue_goldens(W, name):
 
 @pytest.mark.parametrize("wavelet,J,mode,method,y", [
     ("db4", 3, "reflect", "smooth", [2, 5]), ("sym8", 2, "symmetric", "smooth", 4),
-    ("db6", 3, "zero", "integratedgrad", [1, 2]), ("haar", 3, "reflect", "integratedgrad", 3)])
+    ("db6", 3, "zero", "integratedgrad", [1, 2]), ("haar", 3, "reflect", "integratedgrad", 3),
+    ("bior2.2", 2, "reflect", "smooth", [2, 5]), ("bior4.4", 2, "symmetric", "integratedgrad", 3)])
 def test_native_frame_vs_oracle(W, wavelet, J, mode, method, y):
-    """E1/E2 native frame (non-haar SmoothGrad at 224; IG at a non-224 size) vs the oracle."""
+    """E1/E2 native frame (non-haar SmoothGrad at 224; IG at a non-224 size) vs the oracle. The biorthogonal
+    rows (both at 96) take analysis, synthesis and the adjoint-maps pass through one class call with filter
+    sets that differ; the oracle looks the names up in the same table."""
     from oracle import wam_ref
     rs = np.random.RandomState(7)
-    size = 224 if method == "smooth" else 96
+    size = 224 if method == "smooth" and not wavelet.startswith("bior") else 96
     x = torch.tensor(rs.standard_normal((2, 3, size, size)).astype(np.float32))
     m = testmodels.TinySmooth2D()
     fn = wam_ref.smooth_2d if method == "smooth" else wam_ref.ig_2d

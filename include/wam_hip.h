@@ -528,6 +528,46 @@ int wam_visualize3d(int64_t items, int size, int levels, const float* cube, floa
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cross-scale statistics of WAM maps and top-p mask agreement (the reference's top-level utils.py:
+ * get_diagonal, get_mean_pixelwise_variance, rank_images, get_gradients_attribution_on_levels; and
+ * compare_iou_models.ipynb: get_highest_percentage, iou, get_iou_between_wavelets). wam_amd/utils.py
+ * drives them.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* maps [images, size, size] float64, levels = J in [0, 16]. get_diagonal's blocks: detail level j
+ * (j = 0 .. J - 1) is rows and columns [size / 2^(j+1), size / 2^j) (integer division), side n_j; the
+ * approximation block is [0, size / 2^J). Every output may be NULL:
+ *   abs_sums [images, J + 1]: sum |v| over level_0 .. level_{J-1}, then the approximation block;
+ *   var_map  [images, T, T], mean_var [images] (J >= 1, T = target >= 1): each detail block is resized
+ *     with scipy.ndimage.zoom(block, T / n_j, order=1)[:T, :T], var_map = np.var over the J resized
+ *     levels (population variance, mean((v - mean(v))^2) with left-to-right sums), mean_var its mean.
+ * out_len[J] (host): scipy's output length m_j = int(round(n_j * (T / n_j))) per level. The zoom is
+ * scipy's in float64: zoom_j = (n_j - 1) / (m_j - 1), 1 when m_j == 1; output index o samples input
+ * coordinate cc = zoom_j * o (one rounded multiply, no fused contraction) with i0 = floor(cc),
+ * weights w0 = 1 - (cc - i0), w1 = 1 - w0, value = sum over the four taps of (v * w_row) * w_col added
+ * row tap first; a tap outside [0, n_j) has weight 0 (it is read at its mirror image); a sample whose
+ * coordinate rounds above n_j - 1 is 0 (mode 'constant').
+ * Partial sums go to ws (wam_level_stats_ws_bytes(images, size, levels, target) bytes; target = 0
+ * when neither var_map nor mean_var is asked for) and are added in a fixed order: no floating-point
+ * atomics, two calls return the same bits. With var_map NULL nothing is stored for it.
+ * WAM_ERR_SHAPE when some m_j < T (the reference's np.stack fails there); WAM_ERR_INVALID_ARG for a
+ * detail level of side 0 with a variance output, a NULL maps, a short ws; WAM_ERR_UNSUPPORTED for
+ * blocks of 2^31 elements or more (size >= 92682; size >= 46341 when levels == 0, whose one block is the map). */
+int64_t wam_level_stats_ws_bytes(int64_t images, int size, int levels, int target);
+int wam_level_stats(int64_t images, int size, int levels, const double* maps, int target, const int32_t* out_len,
+                    double* abs_sums, double* var_map, double* mean_var, void* ws, int64_t ws_bytes,
+                    void* stream);
+
+/* maps [M, len] float64, thr [M, Q] float64 (device): pixel x of map i is selected at q when
+ * maps[i, x] >= thr[i, q] (a NaN is never selected). inter / uni [Q, M (M - 1) / 2] uint64, pairs
+ * (i < j) in lexicographic order: the number of pixels selected by both maps / by either map. The
+ * call zeroes them itself. M in [2, 16], Q in [1, 16]: WAM_ERR_UNSUPPORTED above (the caller runs
+ * pair and percentage chunks, sized by wam_mask_iou_limits: the two upper bounds of this build). */
+void wam_mask_iou_limits(int* max_maps, int* max_q);
+int wam_mask_iou(int M, int Q, int64_t len, const double* maps, const double* thr, uint64_t* inter, uint64_t* uni,
+                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 1D mel front-end (replaces lib/wam_1D.py:194-219, BaseWAM1D.compute_melspec: torchaudio
  * MelSpectrogram(sample_rate, n_fft, n_mels) with its defaults -- periodic Hann, hop n_fft / 2,
  * center + reflect padding, power 2, HTK mel without normalisation -- followed by AmplitudeToDB()

@@ -79,6 +79,11 @@ _SIGS = {
     "wam_timing_enable": (c_int, [c_int]),
     "wam_copy": (c_int, [c_i64, c_vp, c_vp, c_vp]),
     "wam_visualize3d": (c_int, [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "wam_level_stats_ws_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+    "wam_level_stats": (c_int, [c_i64, c_int, c_int, c_vp, c_int, ctypes.POINTER(ctypes.c_int32), c_vp, c_vp, c_vp,
+                                c_vp, c_i64, c_vp]),
+    "wam_mask_iou_limits": (None, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "wam_mask_iou": (c_int, [c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wam_melspec": (c_int, [c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wam_melspec_adjoint": (c_int, [c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wam_rank_masks": (c_int, [c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp]),

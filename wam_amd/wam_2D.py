@@ -132,6 +132,12 @@ class BaseWAM2D:
             x = torch.as_tensor(np.asarray(x))
         return x.detach().to(self._dev, dtype=torch.float32).contiguous()
 
+    @property
+    def map_device(self):
+        """The float64 device map [N, R, R] of the last SmoothGrad / IG call (what that call returned
+        as a numpy array), or None before the first call. Read by wam_amd.utils."""
+        return getattr(self, "_avg_dev", None)
+
     # ------------------------------------------------------------------ lazy side attributes
     def _record_pass(self, plan, coeff_flat, grad_flat, batch_items, first_item, n, c, coeff_items=None,
                      coeff_first=None, grad_img=None):

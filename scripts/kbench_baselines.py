@@ -102,7 +102,8 @@ def main():
     from tests.golden.imgbase_cases import distinct_positive
     from wam_amd import _lib
     from wam_amd._lib import c_f32, check, lib, ptr, stream_of
-    from wam_amd.baselines import EvalImageBaselines, _cell_map, _ranks, cam_maps
+    from wam_amd.baselines import EvalImageBaselines, cam_maps
+    from wam_amd.evalcore import cell_map, descending_ranks
     from wam_amd.evaluation import IMAGENET_MEAN, IMAGENET_STD
     from wam_amd.plan import timing_drain, timing_enable
 
@@ -113,7 +114,7 @@ def main():
     rs = np.random.RandomState(0)
     imgs = torch.as_tensor(rs.uniform(size=(N, 3, P)).astype(np.float32)).to(dev)
     expl = distinct_positive(rs, (N, P))
-    rank = _ranks(expl, dev, "stable")
+    rank = descending_ranks(expl, dev, "stable")
     mean, std = (c_f32 * 3)(*IMAGENET_MEAN), (c_f32 * 3)(*IMAGENET_STD)
     variant = None
     if a.variant:
@@ -167,7 +168,7 @@ def main():
 
     # ---- 2. superpixel masks -> model inputs
     n, g = a.masks, a.grid
-    cell = _cell_map(g, (S, S), dev)
+    cell = cell_map(g, (S, S), dev)
     grid = torch.as_tensor(rs.uniform(size=(n, g * g)).astype(np.float32)).to(dev)
     img = imgs[0].contiguous()
     out_f = torch.empty((n, 3, P), dtype=torch.float32, device=dev)

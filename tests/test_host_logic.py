@@ -437,6 +437,27 @@ def test_pil_bilinear_tables_reproduce_pillow(hw):
     assert np.array_equal(src.astype(np.uint8), ref)
 
 
+def test_descending_ranks_against_numpy():
+    """The evaluators' one ranking (wam_amd.evalcore.descending_ranks) on the CPU device: rank[order[i]] = i
+    with order = argsort(v)[::-1] ('numpy') or the flipped stable ascending argsort ('stable'), per row of
+    the signed values; three rows with ties, and the one-row call Eval2DWAM makes."""
+    from wam_amd.evalcore import check_tie_order, descending_ranks
+    values = np.random.RandomState(17).randint(-4, 5, (3, 17)).astype(np.float64) / 4
+    values[1, 5:9] = values[1, 0]
+    assert all(len(np.unique(v)) < v.size for v in values)
+    for tie_order in ("stable", "numpy"):
+        want = np.empty(values.shape, dtype=np.int32)
+        for v, w in zip(values, want):
+            order = np.argsort(v)[::-1] if tie_order == "numpy" else np.argsort(v, kind="stable")[::-1]
+            w[order] = np.arange(v.size)
+        for rows in (values, values[2:]):
+            got = descending_ranks(rows, torch.device("cpu"), check_tie_order(tie_order))
+            assert got.dtype == torch.int32 and got.is_contiguous() and tuple(got.shape) == rows.shape
+            assert np.array_equal(got.numpy(), want[-len(rows):])
+    with pytest.raises(ValueError):
+        check_tie_order("first")
+
+
 def test_wam_group_budget():
     """IG / SmoothGrad transform passes: multiples of the model group within the memory budget; the
     default budget is an eighth of the device's HBM, 8-64 GiB (8 GiB without a GPU)."""

@@ -42,9 +42,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import c_f32, c_vp, check, lib, ptr, stream_of
-from .evaluation import (IMAGENET_MEAN, IMAGENET_STD, _LAYOUT, _softmax, array_layout, resize_default,
-                         show_images)
+from ._lib import c_vp, check, lib, ptr, stream_of
+from .evalcore import array_layout, device_table, norm_consts, resize_default, show_images, softmax
 from .plan import get_plan
 from .wam_2D import WaveletAttribution2D
 
@@ -74,16 +73,15 @@ def level_edges(size, J):
 
 def _level_entry_map(size, J, dev):
     """[size * size] int64 on `dev`: the level entry whose region holds each position (-1: none)."""
-    key = ("levels2d", size, J, dev)
-    if key not in _LAYOUT:
+    def make():
         e = level_edges(size, J)
         m = np.maximum(np.arange(size)[:, None], np.arange(size)[None, :])
         entry = np.full((size, size), -1, dtype=np.int64)
         for j in range(J):
             entry[(m >= e[j + 1]) & (m < e[j])] = j
         entry[m < e[J]] = J
-        _LAYOUT[key] = torch.as_tensor(entry.reshape(-1)).to(dev)
-    return _LAYOUT[key]
+        return torch.as_tensor(entry.reshape(-1)).to(dev)
+    return device_table(("levels2d", size, J, dev), make)
 
 
 # ------------------------------------------------------------------------------ thresholds
@@ -269,8 +267,7 @@ class WAMAnalyzer2D(WaveletAttribution2D):
                                                 stream_of(dev)))
             host = u8.view(M, C, rh, rw).permute(0, 2, 3, 1).contiguous().cpu().numpy()
             return torch.stack([transform(self._pil(h)) for h in host]).to(dev), u8
-        mean = (c_f32 * C)(*IMAGENET_MEAN[:C])
-        std = (c_f32 * C)(*IMAGENET_STD[:C])
+        mean, std = norm_consts(C)
         if (rh, rw) == (224, 224):  # Resize((224, 224)) is the identity: one fused pass
             u8 = torch.empty((M, C, rh * rw), dtype=torch.uint8, device=dev)
             out = torch.empty((M, C, rh, rw), dtype=torch.float32, device=dev)
@@ -345,7 +342,7 @@ class WAMAnalyzer2D(WaveletAttribution2D):
             u8 = bytes_[0] if len(bytes_) == 1 else torch.cat(bytes_, dim=1)
             for k, index in enumerate(range(n0, n1)):
                 grad_wam = self.grad_wams[index]
-                probs = _softmax(preds[k])
+                probs = softmax(preds[k])
                 hits = np.where(np.argmax(preds[k], axis=1) == y[index])[0]
                 if not len(hits):
                     outs.append(((None, None, None), None, grad_wam, (None, np.nan)))

@@ -22,9 +22,9 @@ import torch
 from scipy.stats import spearmanr
 
 from . import plan as _plan
-from ._lib import c_f32, check, lib, ptr, stream_of
-from .evaluation import (IMAGENET_MEAN, IMAGENET_STD, _LAYOUT, _softmax, compute_auc, generate_subsets,
-                         resize_default, show_images, zoom_cell_map)
+from ._lib import check, lib, ptr, stream_of
+from .evalcore import (cell_map, check_tie_order, class_curves, class_probs, compute_auc, descending_ranks,
+                       generate_subsets, masked_sums, norm_consts, resize_default, show_images, softmax)
 
 METHODS = ("gradcam", "gradcampp", "saliency", "integratedgrad", "smoothgrad")
 # methods of the reference that need packages this project does not carry
@@ -241,10 +241,6 @@ class IntegratedGradients:
 
 
 # ------------------------------------------------------------------------------------ masked inputs
-def _norm_consts(C):
-    return (c_f32 * C)(*IMAGENET_MEAN[:C]), (c_f32 * C)(*IMAGENET_STD[:C])
-
-
 def _outputs(n, C, P, dev, want):
     """The (masked, u8, out) triple of the two mask entries with only ``want`` allocated."""
     masked = torch.empty((n, C, P), dtype=torch.float32, device=dev) if want == "masked" else None
@@ -258,7 +254,7 @@ def rank_mask_pixels(imgs, rank, n_iter, deletion, want="out"):
     output ('masked', 'u8' or 'out') of all sets * (n_iter + 1) masked images, [sets * (n_iter + 1), C, P]."""
     sets, C, P = imgs.shape
     dev = imgs.device
-    mean, std = _norm_consts(C)
+    mean, std = norm_consts(C)
     masked, u8, out = _outputs(sets * (n_iter + 1), C, P, dev, want)
     ws = torch.empty(int(lib.wam_rank_mask_pixels_ws_bytes(sets, n_iter)) // 4, dtype=torch.float32, device=dev)
     check(lib.wam_rank_mask_pixels(sets, C, P, ptr(imgs.contiguous()), ptr(rank.contiguous()), n_iter, int(P / n_iter),
@@ -272,31 +268,11 @@ def cell_mask_pixels(img, grid_masks, cell, want="out"):
     (device) -> the ``want`` output of the n masked images, [n, C, P]."""
     C, P = img.shape
     n, grid_len = grid_masks.shape
-    mean, std = _norm_consts(C)
+    mean, std = norm_consts(C)
     masked, u8, out = _outputs(n, C, P, img.device, want)
     check(lib.wam_cell_mask_pixels(C, P, ptr(img.contiguous()), n, grid_len, ptr(grid_masks.contiguous()), ptr(cell),
                                    mean, std, ptr(masked), ptr(u8), ptr(out), stream_of(img.device)))
     return {"masked": masked, "u8": u8, "out": out}[want]
-
-
-def _cell_map(grid_size, hw, dev):
-    key = (grid_size, tuple(hw), dev)
-    if key not in _LAYOUT:
-        _LAYOUT[key] = torch.as_tensor(zoom_cell_map(grid_size, hw).astype(np.int32)).to(dev).reshape(-1)
-    return _LAYOUT[key]
-
-
-def _ranks(values, dev, tie_order):
-    """values [sets, P] (host): rank[s, p] = position of pixel p in set s's descending order (the signed
-    values: generate_masks has no abs)."""
-    values = np.ascontiguousarray(values)
-    if tie_order == "numpy":
-        order = torch.as_tensor(np.stack([np.argsort(v, axis=None)[::-1] for v in values])).to(dev)
-    else:
-        order = torch.argsort(torch.as_tensor(values).to(dev), dim=1, stable=True).flip(1)
-    rank = torch.empty_like(order)
-    rank.scatter_(1, order, torch.arange(order.shape[1], device=dev).expand_as(order))
-    return rank.to(torch.int32).contiguous()
 
 
 class EvalImageBaselines:
@@ -333,8 +309,6 @@ class EvalImageBaselines:
                                       % (method_name, _NEEDS[method_name]))
         if method_name not in METHODS:
             raise ValueError("EvalImageBaselines: unknown method %r (one of %s)" % (method_name, ", ".join(METHODS)))
-        if tie_order not in ("stable", "numpy"):
-            raise ValueError("tie_order must be 'stable' or 'numpy'")
         self.transform = transform
         self.random_seed = random_seed
         self.method_name = method_name
@@ -342,7 +316,7 @@ class EvalImageBaselines:
         self.model = model
         self.explanations = None
         self.device = self._dev = _device_of(model)
-        self.tie_order = tie_order
+        self.tie_order = check_tie_order(tie_order)
         self.eval_batch = eval_batch
         self.insertion_curves = []
         self.deletion_curves = []
@@ -367,24 +341,19 @@ class EvalImageBaselines:
             return torch.stack([torch.as_tensor(np.asarray(self.transform(im))).float() for im in ims]).to(self._dev)
         if (H, W) == (224, 224):  # Resize((224, 224)) is the identity: the fused output
             return produce("out").view(n, C, H, W)
-        mean, std = _norm_consts(C)
+        mean, std = norm_consts(C)
         return resize_default(self._dev, produce("masked"), n, C, H, W, mean, std)[0]
-
-    def _probs(self, inputs, label):
-        with torch.no_grad():
-            preds = self.model(inputs).float().cpu().numpy()
-        return _softmax(preds)[:, label]
 
     def _eval_rows(self, inputs, label, n_rows):
         """Class probabilities of the first n_rows inputs, eval_batch rows per forward."""
-        out = [self._probs(inputs[s:min(n_rows, s + self.eval_batch)], label).astype(np.float32)
+        out = [class_probs(self.model, inputs[s:min(n_rows, s + self.eval_batch)], label).astype(np.float32)
                for s in range(0, n_rows, self.eval_batch)]
         return np.concatenate(out) if out else np.empty(0, dtype=np.float32)
 
     def _cell_inputs(self, image, grid_masks, grid_size):
         C, H, W = image.shape
         n = grid_masks.shape[0]
-        cell = _cell_map(grid_size, (H, W), self._dev)
+        cell = cell_map(grid_size, (H, W), self._dev)
         g = torch.as_tensor(np.ascontiguousarray(grid_masks, dtype=np.float32)).to(self._dev).reshape(n, -1)
         img = image.reshape(C, H * W)
         return self._model_inputs(lambda want: cell_mask_pixels(img, g, cell, want), n, C, H, W)
@@ -413,15 +382,15 @@ class EvalImageBaselines:
         for s0 in range(0, n_samples, per_call):
             group = list(range(s0, min(n_samples, s0 + per_call)))
             imgs = torch.stack([images[s] for s in group]).reshape(len(group), C, H * W)
-            rank = _ranks(np.stack([np.asarray(self.explanations[s]).reshape(-1) for s in group]), self._dev,
-                          self.tie_order)
+            rank = descending_ranks(np.stack([np.asarray(self.explanations[s]).reshape(-1) for s in group]),
+                                    self._dev, self.tie_order)
             inputs = self._model_inputs(lambda want: rank_mask_pixels(imgs, rank, n_iter, mode == "deletion", want),
                                         len(group) * M, C, H, W)
             with torch.no_grad():
                 preds = self.model(inputs).float().cpu().numpy()
-            for k, s in enumerate(group):
-                p = _softmax(preds[k * M:(k + 1) * M])[:, y[s]].tolist()
-                scores.append(compute_auc(np.array(p)))
+            for p in class_curves(preds, M, [y[s] for s in group]):
+                p = p.tolist()
+                scores.append(compute_auc(np.array(p)))  # float64, where the WAM evaluators stay in float32
                 predicted_probs.append(p)
         return scores, predicted_probs
 
@@ -450,11 +419,11 @@ class EvalImageBaselines:
         dev = self._dev
         xd = torch.as_tensor(x).detach().to(dev, torch.float32)
         with torch.no_grad():
-            base = _softmax(self.model(xd).float().cpu().numpy())
+            base = softmax(self.model(xd).float().cpu().numpy())
         base_probs = [base[i, y[i]] for i in range(len(y))]
         images = show_images(x, dev)
         H, W = xd.shape[2], xd.shape[3]
-        cell = _cell_map(grid_size, (H, W), dev)
+        cell = cell_map(grid_size, (H, W), dev)
         n_rows = min(sample_size, int(np.ceil(sample_size) / self.batch_size) * self.batch_size)
         mu = []
         for i in range(len(self.explanations)):
@@ -469,9 +438,5 @@ class EvalImageBaselines:
             altered = self._eval_rows(self._cell_inputs(images[i], masks, grid_size), y[i], n_rows)
             preds = base_probs[i] - altered
             expl = torch.as_tensor(np.ascontiguousarray(self.explanations[i]), dtype=torch.float64).to(dev)
-            subd = torch.as_tensor(sub).to(dev)
-            attrs = torch.empty(sample_size, dtype=torch.float64, device=dev)
-            check(lib.wam_masked_sums(sample_size, expl.numel(), ptr(expl), grid_size * grid_size, ptr(subd), ptr(cell),
-                                      ptr(attrs), stream_of(dev)))
-            mu.append(np.nanmean(spearmanr(preds, attrs.cpu().numpy())))
+            mu.append(np.nanmean(spearmanr(preds, masked_sums(expl, sub, cell))))
         return mu

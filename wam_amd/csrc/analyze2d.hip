@@ -7,19 +7,12 @@
 // coefficients of every (image, threshold, channel) plane wam_waverec reads -- the masks are never
 // stored -- and one workgroup per reconstruction does the min / max reduction and the quantisation.
 // Both kernels are HBM-bound streaming passes.
-#include "kernels.hpp"
+#include "maskexpand.hpp"
 #include "quantize.hpp"
 
 namespace {
 
-constexpr int kThrChunk = 16;  // thresholds per blockIdx.y (coefficient, position and map value stay in registers)
-
-struct ThrBands {
-  int nbands;
-  int vec[WAM_MAX_BANDS];           // band offset and length are multiples of 4 floats: 16-byte path
-  int64_t off[WAM_MAX_BANDS + 1];   // per-item element offsets
-  int64_t unit0[WAM_MAX_BANDS + 1]; // first work unit of the band (a unit = 4 elements, or 1 on the scalar path)
-};
+using ThrBands = MaskBands<WAM_MAX_BANDS>;
 
 struct LevelEdges {
   int n;                            // entries (levels + 1)
@@ -56,10 +49,50 @@ __device__ __forceinline__ float keep_mul(double v, double t, bool strict) {
   return (strict ? v > t : v >= t) ? 1.f : 0.f;
 }
 
-// One thread owns 4 consecutive coefficients of one (band, input plane) (1 on the scalar path): it
-// reads them, their array positions and the map values there once, and writes them into the
-// kThrChunk threshold items of its blockIdx.y. For one threshold a wave writes 64 x 16 consecutive
-// bytes. LEVEL: threshold q is level entry q, a map value outside the entry's region counts as 0.
+// mask_expand's policy: an element's fate is the map value of its image at its array position; the
+// "masks" are the thresholds of the image's row, the output item of (plane (n, c), threshold q) is
+// (n * n_thr + q) * channels + c. LEVEL: threshold q is level entry q, a map value outside the entry's
+// region counts as 0.
+template <bool LEVEL>
+struct ThresholdPolicy {
+  int channels;
+  const int32_t* __restrict__ pos;
+  int size;
+  int64_t map_len;
+  const double* __restrict__ wam;
+  int64_t n_thr;
+  const double* __restrict__ thr;
+  int64_t thr_stride;
+  const LevelEdges& le;
+  bool strict;
+  struct Item { int64_t n, c; const double *w, *t; };  // image, channel, the image's map and threshold rows
+  struct Elem { int32_t p; double v; };                // array position, map value there
+  struct Mask { double t; int lo, hi; };               // threshold, the level entry's bounds
+  __device__ Item item(int64_t pl) const {
+    const int64_t n = pl / channels;
+    return {n, pl - n * channels, wam + n * map_len, thr + n * thr_stride};
+  }
+  template <int W>
+  __device__ void load(const Item& it, int64_t bo, int64_t e, Elem (&el)[W]) const {
+    int32_t p[W];
+    load_w<W>(pos + bo + e, p);
+#pragma unroll
+    for (int k = 0; k < W; ++k) el[k] = {p[k], map_value(it.w, p[k], map_len)};
+  }
+  __device__ Mask mask(const Item& it, int64_t q) const {
+    Mask mk{it.t[q], 0, 0};
+    if (LEVEL) level_bounds(le, (int)q, mk.lo, mk.hi);
+    return mk;
+  }
+  __device__ float keep(const Mask& mk, const Elem& el) const {
+    double v = el.v;
+    if (LEVEL && (uint64_t)(int64_t)el.p < (uint64_t)map_len && !in_level(mk.lo, mk.hi, el.p, size)) v = 0.0;
+    return keep_mul(v, mk.t, strict);
+  }
+  __device__ int64_t out_item(const Item& it) const { return it.n * n_thr * channels + it.c; }
+  __device__ int64_t out_step() const { return channels; }
+};
+
 template <bool LEVEL>
 __global__ void __launch_bounds__(256) k_threshold_mask(int64_t images, int channels, ThrBands tb,
                                                         const float* __restrict__ coeffs,
@@ -67,67 +100,14 @@ __global__ void __launch_bounds__(256) k_threshold_mask(int64_t images, int chan
                                                         const double* __restrict__ wam, int64_t n_thr,
                                                         const double* __restrict__ thr, int64_t thr_stride,
                                                         LevelEdges le, int strict, float* __restrict__ out) {
-  const int64_t planes = images * channels;
-  const int64_t map_len = (int64_t)size * size;
-  const int64_t q0 = (int64_t)blockIdx.y * kThrChunk;
-  const int64_t q1 = q0 + kThrChunk < n_thr ? q0 + kThrChunk : n_thr;
-  const bool st = strict != 0;
-  const int64_t units = tb.unit0[tb.nbands];
-  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-    int b = 0;
-#pragma unroll 1
-    while (b + 1 < tb.nbands && u >= tb.unit0[b + 1]) ++b;
-    const int64_t bo = tb.off[b], bn = tb.off[b + 1] - bo;
-    const int64_t r = u - tb.unit0[b];
-    if (tb.vec[b]) {
-      const int64_t per = bn >> 2;
-      const int64_t pl = r / per, e = (r - pl * per) << 2;
-      const int64_t n = pl / channels, c = pl - n * channels;
-      const wam_f4v cf = *reinterpret_cast<const wam_f4v*>(coeffs + planes * bo + pl * bn + e);
-      const int4 p4 = *reinterpret_cast<const int4*>(pos + bo + e);
-      const int32_t p[4] = {p4.x, p4.y, p4.z, p4.w};
-      const double* w = wam + n * map_len;
-      double v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = map_value(w, p[i], map_len);
-      const double* t = thr + n * thr_stride;
-      float* o = out + planes * n_thr * bo + (n * n_thr * channels + c) * bn + e;
-      for (int64_t q = q0; q < q1; ++q) {
-        const double tq = t[q];
-        int lo = 0, hi = 0;
-        if (LEVEL) level_bounds(le, (int)q, lo, hi);
-        float m[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          double vi = v[i];
-          if (LEVEL && (uint64_t)(int64_t)p[i] < (uint64_t)map_len && !in_level(lo, hi, p[i], size)) vi = 0.0;
-          m[i] = keep_mul(vi, tq, st);
-        }
-        *reinterpret_cast<wam_f4v*>(o + q * channels * bn) = wam_f4v{cf.x * m[0], cf.y * m[1], cf.z * m[2], cf.w * m[3]};
-      }
-    } else {
-      const int64_t pl = r / bn, e = r - pl * bn;
-      const int64_t n = pl / channels, c = pl - n * channels;
-      const float cf = coeffs[planes * bo + pl * bn + e];
-      const int32_t p = pos[bo + e];
-      const double v = map_value(wam + n * map_len, p, map_len);
-      const double* t = thr + n * thr_stride;
-      float* o = out + planes * n_thr * bo + (n * n_thr * channels + c) * bn + e;
-      for (int64_t q = q0; q < q1; ++q) {
-        double vi = v;
-        int lo = 0, hi = 0;
-        if (LEVEL) level_bounds(le, (int)q, lo, hi);
-        if (LEVEL && (uint64_t)(int64_t)p < (uint64_t)map_len && !in_level(lo, hi, p, size)) vi = 0.0;
-        o[q * channels * bn] = cf * keep_mul(vi, t[q], st);
-      }
-    }
-  }
+  const ThresholdPolicy<LEVEL> p{channels, pos, size, (int64_t)size * size, wam, n_thr, thr,
+                                 thr_stride, le, strict != 0};
+  mask_expand(p, tb, images * channels, n_thr, coeffs, out, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+              (int64_t)gridDim.x * blockDim.x);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- quantisation of a reconstruction, one workgroup per image (channels x plane floats): the min / max
-// pass (block_minmax), a barrier, then the map (quantize_one, quantize.hpp) on a second read of the image
+// pass (block_reduce), a barrier, then the map (quantize_one, quantize.hpp) on a second read of the image
 
 // VEC: plane is a multiple of 4 and the buffers are 16-byte (u8: 4-byte) aligned, so a thread handles 4
 // consecutive values of one channel per step: a 16-byte load, a 4-byte and a 16-byte store. The values are
@@ -152,7 +132,9 @@ __global__ void __launch_bounds__(1024) k_quantize_ex(int channels, int64_t plan
       mx = fmaxf(mx, x[i]);
     }
   }
-  block_minmax(mn, mx);
+  __shared__ MinMax<float> red[16];
+  const MinMax<float> ext = block_reduce(MinMax<float>{mn, mx}, MinMaxOp(), red);
+  mn = ext.mn, mx = ext.mx;
   uint8_t* b = u8 ? u8 + blockIdx.x * n : nullptr;
   float* o = out ? out + blockIdx.x * n : nullptr;
   if (VEC) {
@@ -191,15 +173,10 @@ void launch_quantize_as(int64_t images, int channels, int64_t plane, const float
 
 int launch_quantize(int64_t images, int channels, int64_t plane, const float* rec, int rule, const float* mean,
                     const float* std, uint8_t* u8, float* out, hipStream_t st) {
-  ChanNorm cn{};
-  for (int c = 0; c < channels && mean && std; ++c) {
-    cn.mean[c] = mean[c];
-    cn.std[c] = std[c];
-  }
+  const ChanNorm cn = chan_norm(channels, mean, std);
   const double px = (double)images * channels * plane;
   const char* name = rule ? "k_quantize_analyzer" : (out ? "k_quantize_normalize" : "k_quantize_u8");
-  const bool vec = (plane & 3) == 0 && aligned16(rec) && (!out || aligned16(out)) &&
-                   (reinterpret_cast<uintptr_t>(u8) & 3) == 0;
+  const bool vec = (plane & 3) == 0 && aligned16(rec) && (!out || aligned16(out)) && aligned4(u8);
   WamTimer tm(st, name, px * (4.0 + (u8 ? 1.0 : 0.0) + (out ? 4.0 : 0.0)));
   if (rule) {
     if (vec) launch_quantize_as<1, true>(images, channels, plane, rec, cn, u8, out, st);
@@ -232,22 +209,12 @@ int wam_threshold_mask_coeffs(const wam_plan* plan, int64_t images, int channels
     for (int j = 0; j < le.n; ++j) le.e[j] = edges[j];
   }
   const int64_t planes = images * channels;
-  const bool ptrs_aligned = aligned16(coeffs) && aligned16(pos) && aligned16(out);
   ThrBands tb{};
-  tb.nbands = plan->nbands;
-  int64_t units = 0;
-  for (int b = 0; b < plan->nbands; ++b) {
-    tb.off[b] = plan->band_off[b];
-    const int64_t bn = plan->band_off[b + 1] - plan->band_off[b];
-    tb.vec[b] = ptrs_aligned && (tb.off[b] & 3) == 0 && (bn & 3) == 0;
-    tb.unit0[b] = units;
-    units += planes * (tb.vec[b] ? bn >> 2 : bn);
-  }
-  tb.off[plan->nbands] = plan->band_off[plan->nbands];
-  tb.unit0[plan->nbands] = units;
+  const int64_t units = fill_mask_bands(tb, plan->nbands, plan->band_off, planes,
+                                        aligned16(coeffs) && aligned16(pos) && aligned16(out));
   if (units == 0) return WAM_OK;
   const int64_t K = tb.off[tb.nbands];
-  const int64_t chunks = (n_thr + kThrChunk - 1) / kThrChunk;
+  const int64_t chunks = (n_thr + kMaskChunk - 1) / kMaskChunk;
   if (chunks > 65535) return WAM_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   // every input read once (the map at the K positions of each image), every output written once

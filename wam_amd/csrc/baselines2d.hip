@@ -7,19 +7,15 @@
 // straight to the quantised, normalised model inputs of every mask, and one workgroup per image does
 // the whole CAM. The mask kernels are HBM-bound streaming passes (write 4 * M * channels * plane bytes
 // per set for 4 * (channels + 1) * plane read).
-#include "kernels.hpp"
+#include "maskexpand.hpp"
 #include "quantize.hpp"
 
 namespace {
 
-constexpr int kMaskChunk = 16;    // masks per blockIdx.y (pixels and ranks stay in registers)
 constexpr int kMaxIter = 4096;    // two [n_iter + 2] tables of bucket extrema in LDS: 32 KB
 constexpr int kMaxSplits = 32;    // workgroups that share the pixels of one set in the extrema pass
 constexpr int kCamLdsCap = 160 * 1024;
 constexpr int kCamGroup = 4;      // channels a wave reduces side by side
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 // order-preserving map of a finite float to uint32, so that LDS integer atomics take float extrema
 __device__ __forceinline__ uint32_t f2ord(float f) {
@@ -30,13 +26,6 @@ __device__ __forceinline__ float ord2f(uint32_t u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 constexpr uint32_t kEmptyMin = 0xffffffffu, kEmptyMax = 0u;  // the images of no finite float
-
-__device__ __forceinline__ int64_t mask_thr(int64_t m, int64_t n_iter, int64_t n_comp, int64_t plane) {
-  if (m == 0) return 0;
-  if (m >= n_iter) return plane;
-  const int64_t t = m * n_comp;
-  return t < plane ? t : plane;
-}
 
 // the first mask m with rank < thr(m): a pixel enters the kept set there (leaves it, under deletion)
 // and stays. n_iter + 1: no mask (a rank outside [0, plane), not part of the contract).
@@ -253,6 +242,7 @@ __global__ void __launch_bounds__(1024) k_cell_mask_pixels(int channels, int64_t
                                                            float* __restrict__ masked, uint8_t* __restrict__ u8,
                                                            float* __restrict__ out) {
   __shared__ float lut[4][256];
+  __shared__ MinMax<float> red[16];
   if (out) fill_norm_lut(lut, channels, cn);
   const int64_t m = blockIdx.x;
   const float* g = grid + m * grid_len;
@@ -288,7 +278,10 @@ __global__ void __launch_bounds__(1024) k_cell_mask_pixels(int channels, int64_t
         }
       }
     }
-    if (pass == 0) block_minmax(mn, mx);
+    if (pass == 0) {
+      const MinMax<float> ext = block_reduce(MinMax<float>{mn, mx}, MinMaxOp(), red);
+      mn = ext.mn, mx = ext.mx;
+    }
   }
 }
 
@@ -297,21 +290,6 @@ __global__ void __launch_bounds__(1024) k_cell_mask_pixels(int channels, int64_t
 // order): channel weights (one wave per channel), the weighted sum over channels (the pixels times as
 // many channel slices as the block holds, reduced through LDS in slice order), ReLU, - min, / max, and
 // torch's bilinear resize (align_corners=False: float32 source coordinates, clamped at 0).
-template <bool MAX>
-__device__ __forceinline__ double block_ext(double v, double* red) {
-  for (int s = 32; s > 0; s >>= 1) {
-    const double o = __shfl_xor(v, s, 64);
-    v = MAX ? fmax(v, o) : fmin(v, o);
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();  // red may still be read from the previous reduction
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  v = red[0];
-  for (int i = 1; i < nw; ++i) v = MAX ? fmax(v, red[i]) : fmin(v, red[i]);
-  return v;
-}
-
 __global__ void __launch_bounds__(1024) k_cam_maps(int K, int h, int w, const float* __restrict__ act,
                                                    const float* __restrict__ grad, int plus_plus, int out_h,
                                                    int out_w, float* __restrict__ out) {
@@ -384,14 +362,14 @@ __global__ void __launch_bounds__(1024) k_cam_maps(int K, int h, int w, const fl
     cam[p] = c;
     mn = fmin(mn, c);
   }
-  mn = block_ext<false>(mn, red);
+  mn = block_reduce(mn, MinOp(), red);
   double mx = -INFINITY;
   for (int p = threadIdx.x; p < hw; p += blockDim.x) {
     const double c = cam[p] - mn;
     cam[p] = c;
     mx = fmax(mx, c);
   }
-  mx = block_ext<true>(mx, red);
+  mx = block_reduce(mx, MaxOp(), red);
   for (int p = threadIdx.x; p < hw; p += blockDim.x) cam[p] = cam[p] / mx;  // 0 / 0 = NaN: the whole map
   __syncthreads();
   const float sh = (float)h / (float)out_h, sw = (float)w / (float)out_w;
@@ -435,15 +413,6 @@ __global__ void __launch_bounds__(256) k_channel_mean(int64_t items, int channel
     if (out_f32) out_f32[t] = m;
     if (acc_f64) acc_f64[t] += (double)m;
   }
-}
-
-ChanNorm chan_norm(int channels, const float* mean, const float* std) {
-  ChanNorm cn{};
-  for (int c = 0; c < channels && mean && std; ++c) {
-    cn.mean[c] = mean[c];
-    cn.std[c] = std[c];
-  }
-  return cn;
 }
 
 }  // namespace

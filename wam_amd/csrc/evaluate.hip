@@ -7,7 +7,7 @@
 // gather pass that writes the band-major buffer the synthesis kernels read (all masks of all
 // channels in one waverec launch), and the byte quantisation + ImageNet normalisation of every
 // reconstruction is one fused pass. All kernels are HBM-bound elementwise / reduction passes.
-#include "kernels.hpp"
+#include "maskexpand.hpp"
 
 namespace {
 
@@ -20,9 +20,7 @@ __global__ void __launch_bounds__(256) k_rank_masks(int64_t n_iter, int64_t n_co
   const int64_t total = (n_iter + 1) * len;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t m = t / len, p = t - m * len;
-    int64_t thr = m >= n_iter ? len : m * n_comp;
-    thr = thr < len ? thr : len;
-    const bool keep = (int64_t)rank[p] < thr;
+    const bool keep = (int64_t)rank[p] < mask_thr(m, n_iter, n_comp, len);
     masks[t] = (keep != (deletion != 0)) ? 1.f : 0.f;
   }
 }
@@ -188,11 +186,7 @@ int launch_pil_resize_norm(int64_t images, int channels, int in_h, int in_w, int
                            const int32_t* kk_v, int y0, int tmp_h, const float* mean, const float* std,
                            uint8_t* scratch, float* out, hipStream_t st) {
   const bool horiz = bounds_h != nullptr, vert = bounds_v != nullptr;
-  ChanNorm cn{};
-  for (int c = 0; c < channels; ++c) {
-    cn.mean[c] = mean[c];
-    cn.std[c] = std[c];
-  }
+  const ChanNorm cn = chan_norm(channels, mean, std);
   const int64_t planes = images * channels;
   const int64_t in_px = planes * (int64_t)in_h * in_w;
   uint8_t* u8 = scratch;                 // planes x in_h x in_w

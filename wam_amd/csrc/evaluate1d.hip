@@ -6,104 +6,61 @@
 // Here the masks are never stored: one pass turns the ranking into the masked band-major
 // coefficients of every (clip, mask) item wam_waverec reads, and one workgroup per reconstruction
 // does the max reduction and the division. All three kernels are HBM-bound streaming passes.
-#include "kernels.hpp"
+#include "maskexpand.hpp"
+#include "quantize.hpp"
 
 namespace {
 
-constexpr int kMaskChunk = 16;               // masks per blockIdx.y (the coefficient is re-read from L2)
 constexpr int kMaxBands1D = 1 + WAM_MAX_LEVELS;
-
-struct RankBands {
-  int nbands;
-  int vec[kMaxBands1D];         // band offset and length are multiples of 4 floats: 16-byte path
-  int64_t off[kMaxBands1D + 1];   // per-item element offsets
-  int64_t unit0[kMaxBands1D + 1]; // first work unit of the band (a unit = 4 elements, or 1 on the scalar path)
-};
-
-__device__ __forceinline__ int64_t mask_thr(int64_t m, int64_t n_iter, int64_t n_comp, int64_t rank_len) {
-  if (m == 0) return 0;
-  if (m >= n_iter) return rank_len;
-  const int64_t t = m * n_comp;
-  return t < rank_len ? t : rank_len;
-}
+using RankBands = MaskBands<kMaxBands1D>;
 
 // a mask slot outside [0, rank_len) is the pad column: rank -1, below every threshold
 __device__ __forceinline__ int32_t slot_rank(const int32_t* __restrict__ rank, int32_t p, int64_t rank_len) {
   return ((uint64_t)(int64_t)p < (uint64_t)rank_len) ? rank[p] : -1;
 }
 
-// One thread owns 4 consecutive coefficients of one (band, set) (1 on the scalar path): it reads
-// them, their mask slots and the slots' ranks once, and writes them into the kMaskChunk mask items of
-// its blockIdx.y. For one mask a wave writes 64 x 16 consecutive bytes. IDENT: the slot of element k
-// is k (wam_rank_mask_rows), pos is not read.
+// mask_expand's policy: an element's fate is the rank of its mask slot pos[k] in its set's row.
+// IDENT: the slot of element k is k (wam_rank_mask_rows), pos is not read.
+template <bool IDENT>
+struct RankPolicy {
+  const int32_t* __restrict__ rank;
+  int64_t rank_len;
+  const int32_t* __restrict__ pos;
+  int64_t n_iter, n_comp;
+  bool del;
+  struct Item { int64_t s; const int32_t* rk; };  // the set and its rank row
+  using Elem = int32_t;
+  using Mask = int64_t;
+  __device__ Item item(int64_t s) const { return {s, rank + s * rank_len}; }
+  template <int W>
+  __device__ void load(const Item& it, int64_t bo, int64_t e, Elem (&rk)[W]) const {
+    if (IDENT) return load_w<W>(it.rk + e, rk);
+    int32_t p[W];
+    load_w<W>(pos + bo + e, p);
+#pragma unroll
+    for (int k = 0; k < W; ++k) rk[k] = slot_rank(it.rk, p[k], rank_len);
+  }
+  __device__ Mask mask(const Item&, int64_t m) const { return mask_thr(m, n_iter, n_comp, rank_len); }
+  __device__ float keep(Mask thr, Elem rk) const { return (((int64_t)rk < thr) != del) ? 1.f : 0.f; }
+  __device__ int64_t out_item(const Item& it) const { return it.s * (n_iter + 1); }
+  __device__ int64_t out_step() const { return 1; }
+};
+
 template <bool IDENT>
 __global__ void __launch_bounds__(256) k_rank_mask(int64_t sets, RankBands rb, const float* __restrict__ coeffs,
                                                    const int32_t* __restrict__ rank, int64_t rank_len,
                                                    const int32_t* __restrict__ pos, int64_t n_iter, int64_t n_comp,
                                                    int deletion, float* __restrict__ out) {
-  const int64_t M = n_iter + 1;
-  const int64_t m0 = (int64_t)blockIdx.y * kMaskChunk;
-  const int64_t m1 = m0 + kMaskChunk < M ? m0 + kMaskChunk : M;
-  const bool del = deletion != 0;
-  const int64_t units = rb.unit0[rb.nbands];
-  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-    int b = 0;
-#pragma unroll 1
-    while (b + 1 < rb.nbands && u >= rb.unit0[b + 1]) ++b;
-    const int64_t bo = rb.off[b], bn = rb.off[b + 1] - bo;
-    const int64_t r = u - rb.unit0[b];
-    if (rb.vec[b]) {
-      const int64_t per = bn >> 2;
-      const int64_t s = r / per, e = (r - s * per) << 2;
-      const wam_f4v c = *reinterpret_cast<const wam_f4v*>(coeffs + sets * bo + s * bn + e);
-      const int32_t* rk_s = rank + s * rank_len;
-      int32_t rk[4];
-      if (IDENT) {
-        const int4 q = *reinterpret_cast<const int4*>(rk_s + e);
-        rk[0] = q.x, rk[1] = q.y, rk[2] = q.z, rk[3] = q.w;
-      } else {
-        const int4 p = *reinterpret_cast<const int4*>(pos + bo + e);
-        rk[0] = slot_rank(rk_s, p.x, rank_len);
-        rk[1] = slot_rank(rk_s, p.y, rank_len);
-        rk[2] = slot_rank(rk_s, p.z, rank_len);
-        rk[3] = slot_rank(rk_s, p.w, rank_len);
-      }
-      float* o = out + sets * M * bo + s * M * bn + e;
-      for (int64_t m = m0; m < m1; ++m) {
-        const int64_t thr = mask_thr(m, n_iter, n_comp, rank_len);
-        wam_f4v v;
-        v.x = c.x * ((((int64_t)rk[0] < thr) != del) ? 1.f : 0.f);
-        v.y = c.y * ((((int64_t)rk[1] < thr) != del) ? 1.f : 0.f);
-        v.z = c.z * ((((int64_t)rk[2] < thr) != del) ? 1.f : 0.f);
-        v.w = c.w * ((((int64_t)rk[3] < thr) != del) ? 1.f : 0.f);
-        *reinterpret_cast<wam_f4v*>(o + m * bn) = v;
-      }
-    } else {
-      const int64_t s = r / bn, e = r - s * bn;
-      const float c = coeffs[sets * bo + s * bn + e];
-      const int32_t rk = IDENT ? rank[s * rank_len + e] : slot_rank(rank + s * rank_len, pos[bo + e], rank_len);
-      float* o = out + sets * M * bo + s * M * bn + e;
-      for (int64_t m = m0; m < m1; ++m) {
-        const int64_t thr = mask_thr(m, n_iter, n_comp, rank_len);
-        o[m * bn] = c * ((((int64_t)rk < thr) != del) ? 1.f : 0.f);
-      }
-    }
-  }
+  const RankPolicy<IDENT> p{rank, rank_len, pos, n_iter, n_comp, deletion != 0};
+  mask_expand(p, rb, sets, n_iter + 1, coeffs, out, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+              (int64_t)gridDim.x * blockDim.x);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int launch_rank_mask(bool ident, int64_t sets, RankBands& rb, bool ptrs_aligned, const float* coeffs,
-                     const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp,
-                     int deletion, float* out, hipStream_t st, const char* name) {
-  int64_t units = 0;
-  for (int b = 0; b < rb.nbands; ++b) {
-    const int64_t bn = rb.off[b + 1] - rb.off[b];
-    rb.vec[b] = ptrs_aligned && (rb.off[b] & 3) == 0 && (bn & 3) == 0;
-    rb.unit0[b] = units;
-    units += sets * (rb.vec[b] ? bn >> 2 : bn);
-  }
-  rb.unit0[rb.nbands] = units;
+int launch_rank_mask(bool ident, int64_t sets, int nbands, const int64_t* band_off, bool ptrs_aligned,
+                     const float* coeffs, const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
+                     int64_t n_comp, int deletion, float* out, hipStream_t st, const char* name) {
+  RankBands rb{};
+  const int64_t units = fill_mask_bands(rb, nbands, band_off, sets, ptrs_aligned);
   if (units == 0) return WAM_OK;
   const int64_t K = rb.off[rb.nbands];
   const int64_t M = n_iter + 1;
@@ -122,17 +79,6 @@ int launch_rank_mask(bool ident, int64_t sets, RankBands& rb, bool ptrs_aligned,
 
 // ---- out = in / max(in), one workgroup per row: wave-64 shuffles, one LDS step, 16-byte loads when
 // the rows are 16-byte aligned; the second read of the row comes from L2.
-__device__ __forceinline__ float block_max(float mx) {
-  __shared__ float smx[16];
-  for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) smx[w] = mx;
-  __syncthreads();
-  mx = smx[0];
-  for (int i = 1; i < nw; ++i) mx = fmaxf(mx, smx[i]);
-  return mx;
-}
-
 __global__ void __launch_bounds__(1024) k_peak_normalize(int64_t len, const float* in, float* out,
                                                          int32_t* __restrict__ silent, int zero_silent, int vec) {
   const float* x = in + blockIdx.x * len;
@@ -148,7 +94,8 @@ __global__ void __launch_bounds__(1024) k_peak_normalize(int64_t len, const floa
   } else {
     for (int64_t i = threadIdx.x; i < len; i += blockDim.x) mx = fmaxf(mx, x[i]);
   }
-  mx = block_max(mx);
+  __shared__ float red[16];
+  mx = block_reduce(mx, MaxOp(), red);
   const bool sil = mx == 0.f;
   if (threadIdx.x == 0 && silent) silent[blockIdx.x] = sil ? 1 : 0;
   if (sil && zero_silent) {
@@ -184,22 +131,17 @@ int wam_rank_mask_coeffs(const wam_plan* plan, int64_t sets, const float* coeffs
     return WAM_ERR_INVALID_ARG;
   if (plan->ndim != 1 || plan->nbands > kMaxBands1D) return WAM_ERR_UNSUPPORTED;
   if (rank_len > INT32_MAX) return WAM_ERR_INVALID_ARG;
-  RankBands rb{};
-  rb.nbands = plan->nbands;
-  for (int b = 0; b <= plan->nbands; ++b) rb.off[b] = plan->band_off[b];
-  return launch_rank_mask(false, sets, rb, aligned16(coeffs) && aligned16(pos) && aligned16(out), coeffs, rank,
-                          rank_len, pos, n_iter, n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_coeffs");
+  const bool ptrs_aligned = aligned16(coeffs) && aligned16(pos) && aligned16(out);
+  return launch_rank_mask(false, sets, plan->nbands, plan->band_off, ptrs_aligned, coeffs, rank, rank_len, pos, n_iter,
+                          n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_coeffs");
 }
 
 int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_t* rank, int64_t n_iter,
                        int64_t n_comp, int deletion, float* out, void* stream) {
   if (sets < 0 || len < 1 || len > INT32_MAX || n_iter < 1 || n_comp < 0 || !src || !rank || !out)
     return WAM_ERR_INVALID_ARG;
-  RankBands rb{};
-  rb.nbands = 1;
-  rb.off[0] = 0;
-  rb.off[1] = len;
-  return launch_rank_mask(true, sets, rb, aligned16(src) && aligned16(rank) && aligned16(out), src, rank, len,
+  const int64_t band_off[2] = {0, len};
+  return launch_rank_mask(true, sets, 1, band_off, aligned16(src) && aligned16(rank) && aligned16(out), src, rank, len,
                           nullptr, n_iter, n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_rows");
 }
 

@@ -109,6 +109,11 @@ int launch_dwt2_adjoint_fold(const wam_plan* p, int64_t batch, int level, const 
 struct ChanNorm {
   float mean[4], std[4];
 };
+inline ChanNorm chan_norm(int channels, const float* mean, const float* std) {  // zeros without constants
+  ChanNorm cn{};
+  for (int c = 0; c < channels && mean && std; ++c) cn.mean[c] = mean[c], cn.std[c] = std[c];
+  return cn;
+}
 
 // Pillow's 8-bit BILINEAR resample + ToTensor / Normalize on quantised bytes (evaluate.hip), shared
 // by wam_quantize_resize_normalize_ex (analyze2d.hip)

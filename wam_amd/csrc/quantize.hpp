@@ -1,27 +1,43 @@
-// The uint8 quantisation shared by the kernels that turn float images into model inputs
-// (analyze2d.hip: reconstructions; baselines2d.hip: pixel-domain masked images).
+// The workgroup min / max reduction and the uint8 quantisation shared by the kernels that turn float
+// images into model inputs (analyze2d.hip: reconstructions; baselines2d.hip: pixel-domain masked images
+// and the CAM's float64 extrema; evaluate1d.hip: the reduction alone, for the peak normalisation).
 #pragma once
 #include "kernels.hpp"
 
-// min / max over the workgroup: wave-64 shuffles, one LDS step. Every thread of the block calls it.
-__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
-  __shared__ float smn[16], smx[16];
-  for (int s = 32; s > 0; s >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, s, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+// What block_reduce combines: a minimum, a maximum (float or double), or both at once as a MinMax pair.
+template <class T>
+struct MinMax {
+  T mn, mx;
+};
+struct MinOp {  // fmin / fmax of two floats are fminf / fmaxf
+  template <class T> __device__ T operator()(T a, T b) const { return fmin(a, b); }
+};
+struct MaxOp {
+  template <class T> __device__ T operator()(T a, T b) const { return fmax(a, b); }
+};
+struct MinMaxOp {
+  template <class T> __device__ MinMax<T> operator()(MinMax<T> a, MinMax<T> b) const {
+    return {fmin(a.mn, b.mn), fmax(a.mx, b.mx)};
   }
+};
+template <class T> __device__ __forceinline__ T wave_xor(T v, int s) { return __shfl_xor(v, s, 64); }
+template <class T> __device__ __forceinline__ MinMax<T> wave_xor(MinMax<T> v, int s) {
+  return {__shfl_xor(v.mn, s, 64), __shfl_xor(v.mx, s, 64)};
+}
+
+// op over the workgroup: a wave-64 xor butterfly, one slot of `red` (LDS, blockDim.x / 64 <= 16 slots)
+// per wave, a serial combine over the waves in order. Every thread of the block calls it and gets the
+// result; the leading barrier lets a kernel call it again on the same `red`.
+template <class V, class Op>
+__device__ __forceinline__ V block_reduce(V v, Op op, V* red) {
+  for (int s = 32; s > 0; s >>= 1) v = op(v, wave_xor(v, s));
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    smn[w] = mn;
-    smx[w] = mx;
-  }
+  __syncthreads();  // red may still be read from the previous reduction
+  if ((threadIdx.x & 63) == 0) red[w] = v;
   __syncthreads();
-  mn = smn[0];
-  mx = smx[0];
-  for (int i = 1; i < nw; ++i) {
-    mn = fminf(mn, smn[i]);
-    mx = fmaxf(mx, smx[i]);
-  }
+  v = red[0];
+  for (int i = 1; i < nw; ++i) v = op(v, red[i]);
+  return v;
 }
 
 // RULE 0: normalize_data (src/evaluation_helpers.py:433-435) -> (x * 255).astype(uint8): min-max,

@@ -36,53 +36,25 @@ The audio evaluator ``Eval1DWAM`` (``src/evaluators.py:39-306``: insertion / del
 coefficients or the mel spectrogram, faithfulness of spectra, input fidelity) closes the module.
 """
 import ctypes
-import math
-import random
 
 import numpy as np
 import torch
-from scipy.ndimage import zoom
 from scipy.stats import spearmanr
 
-from ._lib import c_f32, check, lib, ptr, stream_of
+from ._lib import check, lib, ptr, stream_of
+from .baselines import EvalImageBaselines  # noqa: F401  (the reference keeps it in this module)
+from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, check_tie_order,  # noqa: F401
+                       class_curves, class_probs, coeff_array_layout, compute_auc, descending_ranks, device_table,
+                       generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, resize_default, show_images,
+                       softmax, zoom_cell_map)
 from .melspec import kernel_supported, mel_forward, melspec_db
 from .plan import get_plan
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d
 from .wam_2D import WaveletAttribution2D
 
-IMAGENET_MEAN = (0.485, 0.456, 0.406)
-IMAGENET_STD = (0.229, 0.224, 0.225)
-_LAYOUT = {}
-
 
 # ------------------------------------------------------------------------------ host geometry
-def coeff_array_layout(plan):
-    """pywt.coeffs_to_array positions (row-major flat index) of a plan's band-major item and the
-    array shape: A at [0:ah, 0:aw]; per level (coarsest first) 'da' (= cH, ptwt 'horizontal')
-    rows [ah:ah+dh] x cols [0:dw], 'ad' (cV) rows [0:dh] x cols [aw:aw+dw], 'dd' at
-    [ah:, aw:]; then (ah, aw) += (dh, dw)."""
-    J = plan.levels
-    ah, aw = plan.band_shapes[0]
-    H = ah + sum(plan.band_shapes[1 + 3 * l][0] for l in range(J))
-    W = aw + sum(plan.band_shapes[1 + 3 * l][1] for l in range(J))
-    parts = [(np.arange(ah)[:, None] * W + np.arange(aw)[None, :]).reshape(-1)]
-    for l in range(J):
-        dh, dw = plan.band_shapes[1 + 3 * l + 2]
-        for b, (r0, c0) in enumerate(((ah, 0), (0, aw), (ah, aw))):
-            h, w = plan.band_shapes[1 + 3 * l + b]
-            parts.append(((r0 + np.arange(h))[:, None] * W + (c0 + np.arange(w))[None, :]).reshape(-1))
-        ah, aw = ah + dh, aw + dw
-    return np.concatenate(parts), (H, W)
-
-
-def zoom_cell_map(grid, hw):
-    """scipy.ndimage.zoom(masks, (1, H / grid, W / grid), order=0) as a per-pixel grid-cell
-    index map (zoom of the cell-index grid: nearest neighbour copies values exactly)."""
-    idx = np.arange(grid * grid, dtype=np.float64).reshape(1, grid, grid)
-    return zoom(idx, (1, hw[0] / grid, hw[1] / grid), order=0)[0].astype(np.int64)
-
-
 def gaussian_weights(sigma, truncate=4.0):
     """scipy's _gaussian_kernel1d(sigma, 0, int(truncate * sigma + 0.5)): w[j] for |offset| j."""
     r = int(truncate * float(sigma) + 0.5)
@@ -90,105 +62,6 @@ def gaussian_weights(sigma, truncate=4.0):
     phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
     phi = phi / phi.sum()
     return phi[r:], r
-
-
-def _softmax(preds):
-    return np.exp(preds) / np.sum(np.exp(preds), axis=1, keepdims=True)
-
-
-def compute_auc(probs):
-    """src/evaluation_helpers.py:437-453."""
-    return sum(probs) / (np.max(probs) * len(probs))
-
-
-def generate_subsets(grid_size, subset_size, sample_size):
-    """src/evaluation_helpers.py:580-594 (Python's global random, as the reference)."""
-    return [[(i // grid_size, i % grid_size) for i in random.sample(range(grid_size * grid_size), subset_size)]
-            for _ in range(sample_size)]
-
-
-def pil_bilinear_coeffs(in_size, out_size):
-    """Pillow's resample tables for BILINEAR along one axis (libImaging/Resample.c precompute_coeffs
-    with box (0, in_size), then normalize_coeffs_8bpc): (ksize, bounds [out, 2] = (first source
-    index, count), 22-bit fixed-point weights [out, ksize] int64, C truncation of w * 2^22 +- 0.5)."""
-    scale = in_size / out_size
-    filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale                      # the triangle filter's support is 1
-    ksize = int(math.ceil(support)) * 2 + 1
-    kk = np.zeros((out_size, ksize))
-    bounds = np.zeros((out_size, 2), dtype=np.int64)
-    ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
-        ww = 0.0
-        for x in range(xmax):
-            t = abs((x + xmin - center + 0.5) * ss)
-            w = 1.0 - t if t < 1.0 else 0.0
-            kk[xx, x] = w
-            ww += w
-        if ww != 0.0:
-            kk[xx, :xmax] /= ww
-        bounds[xx] = (xmin, xmax)
-    fixed = np.trunc(np.where(kk < 0, -0.5 + kk * (1 << 22), 0.5 + kk * (1 << 22))).astype(np.int64)
-    return ksize, bounds, fixed
-
-
-def show_images(x, dev):
-    """show(x[i]) (src/helpers.py:421-448) on the device: a list of [3, H, W] float32 tensors, min-max
-    normalised per image when outside [0, 1] (numpy: img -= min; img /= max)."""
-    xd = torch.as_tensor(x).detach().to(dev, torch.float32).contiguous()
-    out = []
-    for i in range(xd.shape[0]):
-        img = xd[i]
-        mn, mx = img.min(), img.max()
-        if bool(mx > 1) or bool(mn < 0):
-            img = img - mn
-            img = img / img.max()
-        out.append(img)
-    return out
-
-
-def array_layout(plan, dev):
-    """coeff_array_layout of a plan as (int32 positions on `dev`, array shape), cached."""
-    key = (plan, dev)
-    if key not in _LAYOUT:
-        pos, shape = coeff_array_layout(plan)
-        _LAYOUT[key] = (torch.as_tensor(pos.astype(np.int32)).to(dev), shape)
-    return _LAYOUT[key]
-
-
-def resize_default(dev, rec, M, C, rh, rw, mean, std, size=(224, 224), rule=0):
-    """The default transform on a reconstruction of another size: uint8 quantisation (rule 0: min-max,
-    rule 1: the analyzer's), Pillow's BILINEAR resample to 224 x 224 (what torchvision's Resize does to
-    the reference's PIL image) and ToTensor + Normalize, on the device
-    (wam_quantize_resize_normalize_ex). Returns (model inputs, the quantised bytes [M, C, rh * rw])."""
-    oh, ow = size
-    th = tv = None
-    if ow != rw:
-        th = pil_bilinear_coeffs(rw, ow)
-    if oh != rh:
-        tv = pil_bilinear_coeffs(rh, oh)
-    y0, tmp_h = 0, rh
-    if th is not None and tv is not None:  # the horizontal pass covers the rows the vertical one reads
-        b = tv[1]
-        y0, tmp_h = int(b[0, 0]), int(b[-1, 0] + b[-1, 1] - b[0, 0])
-        tv = (tv[0], b - np.array([y0, 0], dtype=b.dtype), tv[2])
-    dv = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
-    bh = kh = bv = kv = None
-    if th is not None:
-        bh, kh = dv(th[1]), dv(th[2])
-    if tv is not None:
-        bv, kv = dv(tv[1]), dv(tv[2])
-    scratch = torch.empty(M * C * (rh * rw + (tmp_h * ow if th is not None else 0)) + 16, dtype=torch.uint8,
-                          device=dev)
-    out = torch.empty((M, C, oh, ow), dtype=torch.float32, device=dev)
-    p_ = lambda t: None if t is None else ptr(t)  # noqa: E731
-    check(lib.wam_quantize_resize_normalize_ex(M, C, rh, rw, ptr(rec), rule, oh, ow, th[0] if th else 0, p_(bh),
-                                               p_(kh), tv[0] if tv else 0, p_(bv), p_(kv), y0, tmp_h, mean, std,
-                                               ptr(scratch), ptr(out), stream_of(dev)))
-    return out, scratch[:M * C * rh * rw].view(M, C, rh * rw)
 
 
 class Eval2DWAM(WaveletAttribution2D):
@@ -205,9 +78,7 @@ class Eval2DWAM(WaveletAttribution2D):
         self.batch_size = batch_size
         self.grad_wams = None
         self.transform = transform
-        if tie_order not in ("stable", "numpy"):
-            raise ValueError("tie_order must be 'stable' or 'numpy'")
-        self.tie_order = tie_order
+        self.tie_order = check_tie_order(tie_order)
         self.eval_batch = eval_batch
         self.insertion_curves = []
         self.deletion_curves = []
@@ -238,8 +109,7 @@ class Eval2DWAM(WaveletAttribution2D):
         rh, rw = plan.rec_shape
         if self.transform is not None:
             return self._host_transform(rec.view(M, C, rh, rw))
-        mean = (c_f32 * C)(*IMAGENET_MEAN[:C])
-        std = (c_f32 * C)(*IMAGENET_STD[:C])
+        mean, std = norm_consts(C)
         if (rh, rw) == (224, 224):  # Resize((224, 224)) is the identity: one fused pass
             out = torch.empty((M, C, rh, rw), dtype=torch.float32, device=dev)
             check(lib.wam_quantize_normalize(M, C, rh * rw, ptr(rec), mean, std, ptr(out), stream_of(dev)))
@@ -260,35 +130,16 @@ class Eval2DWAM(WaveletAttribution2D):
             out.append(torch.as_tensor(np.asarray(self.transform(Image.fromarray(u8)))).float())
         return torch.stack(out).to(self._dev)
 
-    def _probs(self, inputs, label):
-        """Model forward (no grad) -> the reference's host softmax -> probabilities of `label`."""
-        with torch.no_grad():
-            preds = self.model(inputs).float().cpu().numpy()
-        return _softmax(preds)[:, label]
-
-    def _ranks(self, wam):
-        """rank[p] = position of pixel p in the descending importance order."""
-        flat = torch.as_tensor(np.ascontiguousarray(wam)).reshape(-1)
-        if self.tie_order == "numpy":
-            order = torch.as_tensor(np.argsort(flat.numpy(), axis=None)[::-1].copy()).to(self._dev)
-        else:
-            order = torch.argsort(flat.to(self._dev), stable=True).flip(0)
-        rank = torch.empty_like(order)
-        rank[order] = torch.arange(order.numel(), device=self._dev)
-        return rank.to(torch.int32)
-
     def _rank_masks(self, wam, n_iter, deletion):
         hw = wam.shape[-2] * wam.shape[-1]
+        rank = descending_ranks(np.reshape(wam, (1, -1)), self._dev, self.tie_order)
         masks = torch.empty((n_iter + 1, wam.shape[-2], wam.shape[-1]), dtype=torch.float32, device=self._dev)
-        check(lib.wam_rank_masks(n_iter, int(hw / n_iter), hw, ptr(self._ranks(wam)), int(bool(deletion)),
-                                 ptr(masks), stream_of(self._dev)))
+        check(lib.wam_rank_masks(n_iter, int(hw / n_iter), hw, ptr(rank), int(bool(deletion)), ptr(masks),
+                                 stream_of(self._dev)))
         return masks
 
     def _upsample(self, grid_masks, grid_size, hw):
-        key = (grid_size, tuple(hw), self._dev)
-        if key not in _LAYOUT:
-            _LAYOUT[key] = torch.as_tensor(zoom_cell_map(grid_size, hw).astype(np.int32)).to(self._dev).reshape(-1)
-        cell = _LAYOUT[key]
+        cell = cell_map(grid_size, hw, self._dev)
         g = torch.as_tensor(np.ascontiguousarray(grid_masks), dtype=torch.float32).to(self._dev)
         out = torch.empty((g.shape[0],) + tuple(hw), dtype=torch.float32, device=self._dev)
         check(lib.wam_upsample_masks(g.shape[0], grid_size * grid_size, ptr(g), hw[0] * hw[1], ptr(cell), ptr(out),
@@ -301,7 +152,7 @@ class Eval2DWAM(WaveletAttribution2D):
         out = []
         for b in range(int(np.ceil(n) / batch_size)):
             s, e = b * batch_size, min(n, (b + 1) * batch_size)
-            out.append(self._probs(images[s:e], label).astype(np.float32))
+            out.append(class_probs(self.model, images[s:e], label).astype(np.float32))
         return np.concatenate(out) if out else np.empty(0, dtype=np.float32)
 
     # -------------------------------------------------------------------- reference API
@@ -319,8 +170,7 @@ class Eval2DWAM(WaveletAttribution2D):
                      for s in range(s0, min(n_samples, s0 + per_call))]
             with torch.no_grad():
                 preds = self.model(torch.cat(batch)).float().cpu().numpy()
-            for k, s in enumerate(range(s0, s0 + len(batch))):
-                p = _softmax(preds[k * (n_iter + 1):(k + 1) * (n_iter + 1)])[:, y[s]]
+            for p in class_curves(preds, n_iter + 1, [y[s] for s in range(s0, s0 + len(batch))]):
                 scores.append(compute_auc(p))
                 predicted_probs.append(p)
         return scores, predicted_probs
@@ -342,7 +192,7 @@ class Eval2DWAM(WaveletAttribution2D):
         np.random.seed(self.random_seed)
         xd = torch.as_tensor(x).detach().to(self._dev, torch.float32)
         with torch.no_grad():
-            base = _softmax(self.model(xd).float().cpu().numpy())
+            base = softmax(self.model(xd).float().cpu().numpy())
         base_probs = [base[i, y[i]] for i in range(len(y))]
         images = self._images(x)
         H, W = xd.shape[2], xd.shape[3]
@@ -368,11 +218,7 @@ class Eval2DWAM(WaveletAttribution2D):
             for j, index_set in enumerate(indices):
                 cx, cy = zip(*index_set)
                 sub[j, cx, cy] = 1
-            subd = torch.as_tensor(sub).to(dev)
-            attrs = torch.empty(sample_size, dtype=torch.float64, device=dev)
-            check(lib.wam_masked_sums(sample_size, wam.numel(), ptr(wam), grid_size * grid_size, ptr(subd), ptr(cell),
-                                      ptr(attrs), stream_of(dev)))
-            mu.append(np.nanmean(spearmanr(preds, attrs.cpu().numpy())))
+            mu.append(np.nanmean(spearmanr(preds, masked_sums(wam, sub, cell))))
         return mu
 
     def compute_baseline_state(self, image, label, grid_size, batch_size, sample_size):
@@ -447,11 +293,9 @@ class Eval1DWAM(WaveletAttribution1D):
                                             approx_coeffs=approx_coeffs, n_mels=n_mels, n_fft=n_fft,
                                             sample_rate=sample_rate, n_samples=n_samples, stdev_spread=stdev_spread,
                                             random_seed=random_seed, **wam_kw)
-        if tie_order not in ("stable", "numpy"):
-            raise ValueError("tie_order must be 'stable' or 'numpy'")
         if silent not in ("nan", "zero"):
             raise ValueError("silent must be 'nan' or 'zero'")
-        self.tie_order = tie_order
+        self.tie_order = check_tie_order(tie_order)
         self.eval_batch = eval_batch
         self.silent = silent
         self.insertion_curve = []   # the reference's constructor names
@@ -460,23 +304,9 @@ class Eval1DWAM(WaveletAttribution1D):
         self.deletion_curves = []
 
     # -------------------------------------------------------------------- device pipeline
-    def _ranks(self, values):
-        """values [sets, len] (host): rank[s, p] = position of slot p in set s's descending order."""
-        values = np.ascontiguousarray(values)
-        if self.tie_order == "numpy":
-            order = torch.as_tensor(np.stack([np.argsort(v)[::-1] for v in values])).to(self._dev)
-        else:
-            order = torch.argsort(torch.as_tensor(values).to(self._dev), dim=1, stable=True).flip(1)
-        rank = torch.empty_like(order)
-        rank.scatter_(1, order, torch.arange(order.shape[1], device=self._dev).expand_as(order))
-        return rank.to(torch.int32).contiguous()
-
     def _slot_map(self, plan, n_masks):
-        key = ("slots1d", plan, self._dev)
-        if key not in _LAYOUT:
-            pos = coeff_slot_map(plan.shape[0], self.J, [s[0] for s in plan.band_shapes], n_masks)
-            _LAYOUT[key] = torch.as_tensor(pos).to(self._dev)
-        return _LAYOUT[key]
+        return device_table(("slots1d", plan, self._dev), lambda: torch.as_tensor(
+            coeff_slot_map(plan.shape[0], self.J, [s[0] for s in plan.band_shapes], n_masks)).to(self._dev))
 
     def _mel(self, wave):
         if kernel_supported(self.n_fft, self.n_mels):
@@ -500,7 +330,7 @@ class Eval1DWAM(WaveletAttribution1D):
         g = np.stack([np.concatenate([np.asarray(b)[s] for b in gradients]) for s in samples])
         if g.shape[1] != K:
             raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,%d)" % (K, M, g.shape[1]))
-        rank = self._ranks(np.abs(g))
+        rank = descending_ranks(np.abs(g), dev, self.tie_order)
         coeffs = plan.wavedec(wave)
         masked = torch.empty(sets * M * K, dtype=torch.float32, device=dev)
         check(lib.wam_rank_mask_coeffs(plan.handle, sets, ptr(coeffs), ptr(rank), K, ptr(pos), n_iter, int(K / n_iter),
@@ -520,7 +350,7 @@ class Eval1DWAM(WaveletAttribution1D):
         grad = grad.reshape((-1,) + grad.shape[-2:])
         src = torch.as_tensor(source_melspec).detach().to(dev, torch.float32).reshape(grad.shape).contiguous()
         sets, n = grad.shape[0], grad.shape[1] * grad.shape[2]
-        rank = self._ranks(grad.reshape(sets, n))  # the signed gradient (generate_masks has no abs)
+        rank = descending_ranks(grad.reshape(sets, n), dev, self.tie_order)  # signed: generate_masks has no abs
         out = torch.empty((sets * (n_iter + 1), 1) + grad.shape[1:], dtype=torch.float32, device=dev)
         check(lib.wam_rank_mask_rows(sets, n, ptr(src), ptr(rank), n_iter, int(n / n_iter), int(mode == "deletion"),
                                      ptr(out), stream_of(dev)))
@@ -555,10 +385,8 @@ class Eval1DWAM(WaveletAttribution1D):
                 if self._silent_rows is not None and self.silent == "nan":
                     logits[self._silent_rows] = float("nan")
                 preds = logits.cpu().numpy()
-                for k, s in enumerate(group):
-                    p = preds[k * M:(k + 1) * M]
-                    raw_preds.append(p)
-                    prob = _softmax(p)[:, y[s]]
+                raw_preds.extend(preds.reshape(len(group), M, -1))
+                for prob in class_curves(preds, M, [y[s] for s in group]):
                     scores.append(compute_auc(prob))
                     predicted_probs.append(prob)
         if argmax:
@@ -587,12 +415,3 @@ class Eval1DWAM(WaveletAttribution1D):
         components inserted (insertion with n_iter = 2, rows 1 and 2)."""
         preds = np.array(self.evaluate_auc(x, y, "insertion", target, 2, argmax=True))
         return np.argmax(preds[:, 1:, :], axis=2).tolist()
-
-
-def __getattr__(name):
-    """``EvalImageBaselines`` (the reference keeps it in the same module) lives in wam_amd.baselines,
-    which builds on this module."""
-    if name == "EvalImageBaselines":
-        from .baselines import EvalImageBaselines
-        return EvalImageBaselines
-    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -511,6 +511,24 @@ int wam_cell_mask_pixels(int channels, int64_t plane, const float* img, int64_t 
  * + 1040) bytes of LDS, WAM_ERR_UNSUPPORTED above 160 KiB. */
 int wam_cam_maps(int64_t images, int64_t K, int h, int w, const float* act, const float* grad, int plus_plus,
                  int out_h, int out_w, float* out, void* stream);
+/* The same maps without the LDS bound: any K >= 1 and any h * w <= INT32_MAX, the shapes wam_cam_maps
+ * accepts included (full-resolution layers of audio CNNs: 157 x 128 and 431 x 128 mel cells; layer1 of
+ * an image ResNet from 640 x 640 inputs up). The contract of the values is the one above, word for word
+ * (float64 sums, normalisation and interpolation, one rounding to float32, the all-NaN map); the order of
+ * the float64 sums differs from wam_cam_maps, so the two agree to rounding of the float32 result, not in
+ * bits. Three launches in stream order: per (image, channel) the weight sums of S = min(64, ceil(h * w /
+ * 1024)) splits of the plane, one wave each; per tile of 1024 pixels the weighted sum over k ascending
+ * (the splits combined in split order), ReLU, the float64 plane and the tile's extrema; the resize, which
+ * reads the plane back. ws (device, 8-byte aligned, written by the call, no initialisation needed):
+ * wam_cam_maps_tiled_ws_bytes(images, K, h, w) = 8 * images * (2 * K * S + h * w + 2 * T) bytes with
+ * T = ceil(h * w / 1024) (the partial sums, the plane, the tile extrema); negative for invalid arguments.
+ * No floating-point atomics: two calls return the same bits. 16-byte loads when h * w % 4 == 0 and act
+ * and grad are 16-byte aligned, scalar ones otherwise; the values are the same. Argument errors as for
+ * wam_cam_maps, and WAM_ERR_INVALID_ARG for a NULL, misaligned or short ws; images == 0 returns WAM_OK
+ * before ws is looked at. */
+int64_t wam_cam_maps_tiled_ws_bytes(int64_t images, int64_t K, int h, int w);
+int wam_cam_maps_tiled(int64_t images, int64_t K, int h, int w, const float* act, const float* grad,
+                       int plus_plus, int out_h, int out_w, float* out, void* ws, int64_t ws_bytes, void* stream);
 /* The channel mean the gradient methods end in. g [items, channels, plane] float32; t_c = g[n, c, p],
  * times mult[n, c, p] when mult != NULL (same shape), then its absolute value when absolute != 0;
  * m = ((t_0 + t_1) + ...) / channels in float32, sequential (numpy's order for a short axis).

@@ -112,6 +112,9 @@ _SIGS = {
     "wam_cell_mask_pixels": (c_int, [c_int, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_f32),
                                      ctypes.POINTER(c_f32), c_vp, c_vp, c_vp, c_vp]),
     "wam_cam_maps": (c_int, [c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "wam_cam_maps_tiled_ws_bytes": (c_i64, [c_i64, c_i64, c_int, c_int]),
+    "wam_cam_maps_tiled": (c_int, [c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_i64,
+                                   c_vp]),
     "wam_channel_mean": (c_int, [c_i64, c_int, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "wam_ew_bias_act": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int, c_vp]),
     "wam_ew_add_bias_relu": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -11,7 +11,8 @@ forward and backward stay in PyTorch; everything after them runs on the HIP kern
   n_iter + 1 insertion (deletion) masks of several images (the masks and the masked float images never
   reach memory); superpixel grids --wam_cell_mask_pixels--> the same for mu-fidelity's masks;
   activations and gradients of the target layer --wam_cam_maps--> Grad-CAM(++) maps, one workgroup per
-  image; input gradients --wam_channel_mean--> the [N, H, W] maps of Saliency, Integrated Gradients
+  image (--wam_cam_maps_tiled, ``csrc/cam_tiled.hip``--> where the layer's map is past that kernel's LDS
+  bound: full-resolution layers); input gradients --wam_channel_mean--> the [N, H, W] maps of Saliency, Integrated Gradients
   (steps summed by wam_trapz_f32) and SmoothGrad (noise by wam_item_sigma + wam_noise_add).
 
 Host work left: the ranking's ``tie_order='numpy'`` option, Python / numpy RNG draws (the reference's
@@ -119,12 +120,29 @@ class GradCAMPlusPlus(GradCAM):
     plus_plus = True
 
 
+CAM_LDS_CAP = 160 * 1024  # wam_cam_maps holds 8 * (K + h * w + 1040) bytes in one workgroup's LDS
+
+
 def cam_maps(act, grad, plus_plus, size):
-    """wam_cam_maps: act, grad [N, K, h, w] float32 (device) -> [N, size[0], size[1]] float32."""
+    """act, grad [N, K, h, w] float32 (device) -> [N, size[0], size[1]] float32: wam_cam_maps while the
+    layer's map fits its LDS bound, wam_cam_maps_tiled (the plane in a workspace) above it."""
     N, K, h, w = act.shape
+    if 8 * (K + h * w + 1040) > CAM_LDS_CAP:
+        return cam_maps_tiled(act, grad, plus_plus, size)
     out = torch.empty((N, size[0], size[1]), dtype=torch.float32, device=act.device)
     check(lib.wam_cam_maps(N, K, h, w, ptr(act), ptr(grad), int(bool(plus_plus)), size[0], size[1], ptr(out),
                            stream_of(act.device)))
+    return out
+
+
+def cam_maps_tiled(act, grad, plus_plus, size):
+    """wam_cam_maps_tiled: the same maps for any K and h * w."""
+    N, K, h, w = act.shape
+    out = torch.empty((N, size[0], size[1]), dtype=torch.float32, device=act.device)
+    nbytes = int(lib.wam_cam_maps_tiled_ws_bytes(N, K, h, w))
+    ws = torch.empty(max(nbytes, 0) // 8, dtype=torch.float64, device=act.device)
+    check(lib.wam_cam_maps_tiled(N, K, h, w, ptr(act), ptr(grad), int(bool(plus_plus)), size[0], size[1], ptr(out),
+                                 ptr(ws), nbytes, stream_of(act.device)))
     return out
 
 

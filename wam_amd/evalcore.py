@@ -1,5 +1,6 @@
-"""What the evaluators (evaluation.py, baselines.py, analysis.py) share on the host: rankings, the
-softmax / AUC of stacked logits, cached device tables (array layout, superpixel cell map), the
+"""What the evaluators (evaluation.py, baselines.py, baselines_audio.py, analysis.py) share on the host:
+rankings, the audio evaluators' ranking-to-masked-rows step and source spectrogram, the softmax / AUC of
+stacked logits, cached device tables (array layout, superpixel cell map), the
 show() normalisation, the default transform's resize and the ImageNet constants."""
 import math
 import random
@@ -9,6 +10,7 @@ import torch
 from scipy.ndimage import zoom
 
 from ._lib import c_f32, check, lib, ptr, stream_of
+from .melspec import kernel_supported, mel_forward, melspec_db
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -39,6 +41,30 @@ def descending_ranks(values, dev, tie_order):
     rank = torch.empty_like(order)
     rank.scatter_(1, order, torch.arange(order.shape[1], device=dev).expand_as(order))
     return rank.to(torch.int32).contiguous()
+
+
+def rank_mask_rows(explanation, source, n_iter, deletion, dev, tie_order):
+    """auc_from_melspec of both audio evaluators (src/evaluators.py:145-176, 394-425) for one clip
+    ([T, n_mels] explanation and dB mel spectrogram) or a batch of clips ([sets, T, n_mels]): the ranking
+    of the signed explanation (generate_masks has no abs) --wam_rank_mask_rows--> the n_iter + 1 masked
+    spectrograms of every clip, [sets * (n_iter + 1), 1, T, n_mels] float32 on the device."""
+    expl = np.asarray(explanation)
+    expl = expl.reshape((-1,) + expl.shape[-2:])
+    src = torch.as_tensor(source).detach().to(dev, torch.float32).reshape(expl.shape).contiguous()
+    sets, n = expl.shape[0], expl.shape[1] * expl.shape[2]
+    rank = descending_ranks(expl.reshape(sets, n), dev, tie_order)
+    out = torch.empty((sets * (n_iter + 1), 1) + expl.shape[1:], dtype=torch.float32, device=dev)
+    check(lib.wam_rank_mask_rows(sets, n, ptr(src), ptr(rank), n_iter, int(n / n_iter), int(bool(deletion)), ptr(out),
+                                 stream_of(dev)))
+    return out
+
+
+def db_melspec(wave, n_fft, sample_rate, n_mels):
+    """The dB mel spectrogram the audio evaluators mask, wave [N, L] float32 (device) -> [N, 1, T, n_mels]:
+    k_mel_fwd where it applies, else the torch path."""
+    if kernel_supported(n_fft, n_mels):
+        return mel_forward(wave, n_fft, sample_rate, n_mels).unsqueeze(1)
+    return melspec_db(wave, n_fft, sample_rate, n_mels)
 
 
 def softmax(preds):

@@ -43,11 +43,11 @@ from scipy.stats import spearmanr
 
 from ._lib import check, lib, ptr, stream_of
 from .baselines import EvalImageBaselines  # noqa: F401  (the reference keeps it in this module)
+from .baselines_audio import EvalAudioBaselines  # noqa: F401  (likewise)
 from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, check_tie_order,  # noqa: F401
-                       class_curves, class_probs, coeff_array_layout, compute_auc, descending_ranks, device_table,
-                       generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, resize_default, show_images,
-                       softmax, zoom_cell_map)
-from .melspec import kernel_supported, mel_forward, melspec_db
+                       class_curves, class_probs, coeff_array_layout, compute_auc, db_melspec, descending_ranks,
+                       device_table, generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, rank_mask_rows,
+                       resize_default, show_images, softmax, zoom_cell_map)
 from .plan import get_plan
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d
@@ -309,9 +309,7 @@ class Eval1DWAM(WaveletAttribution1D):
             coeff_slot_map(plan.shape[0], self.J, [s[0] for s in plan.band_shapes], n_masks)).to(self._dev))
 
     def _mel(self, wave):
-        if kernel_supported(self.n_fft, self.n_mels):
-            return mel_forward(wave, self.n_fft, self.sample_rate, self.n_mels).unsqueeze(1)
-        return melspec_db(wave, self.n_fft, self.sample_rate, self.n_mels)
+        return db_melspec(wave, self.n_fft, self.sample_rate, self.n_mels)
 
     def auc_from_wavelet(self, gradients, waveform, sample, mode, n_iter):
         """src/evaluators.py:56-143 for the clips `sample` (an index or a sequence of indices) of
@@ -345,17 +343,8 @@ class Eval1DWAM(WaveletAttribution1D):
     def auc_from_melspec(self, melspec, source_melspec, mode, n_iter):
         """src/evaluators.py:145-176 for one clip ([T, n_mels] gradients and dB mel spectrogram) or a
         batch of clips ([sets, T, n_mels]): [sets * (n_iter + 1), 1, T, n_mels] on the device."""
-        dev = self._dev
-        grad = np.asarray(melspec)
-        grad = grad.reshape((-1,) + grad.shape[-2:])
-        src = torch.as_tensor(source_melspec).detach().to(dev, torch.float32).reshape(grad.shape).contiguous()
-        sets, n = grad.shape[0], grad.shape[1] * grad.shape[2]
-        rank = descending_ranks(grad.reshape(sets, n), dev, self.tie_order)  # signed: generate_masks has no abs
-        out = torch.empty((sets * (n_iter + 1), 1) + grad.shape[1:], dtype=torch.float32, device=dev)
-        check(lib.wam_rank_mask_rows(sets, n, ptr(src), ptr(rank), n_iter, int(n / n_iter), int(mode == "deletion"),
-                                     ptr(out), stream_of(dev)))
         self._silent_rows = None
-        return out
+        return rank_mask_rows(melspec, source_melspec, n_iter, mode == "deletion", self._dev, self.tie_order)
 
     # -------------------------------------------------------------------- reference API
     def evaluate_auc(self, x, y, mode, target, n_iter=64, argmax=False):

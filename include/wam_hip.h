@@ -612,6 +612,9 @@ int wam_melspec_adjoint(int64_t items, int64_t samples, int n_fft, int n_mels, i
  * dtype: WAM_DT_F32 or WAM_DT_BF16 (storage; arithmetic is fp32). Tensors are contiguous with n
  * elements; the channel of element i is (i / inner) % channels (inner = 1: NHWC, H*W: NCHW).
  * Bias vectors (length channels, same dtype) may be NULL (= 0). out may alias an input.
+ * Special values: the forward ReLU is v < 0 ? 0 : v, so a NaN sum stays NaN (as torch.relu; max(v, 0)
+ * below is written in that sense) and -0.0 may come out as either zero; the mask y > 0 ? g : 0 is 0
+ * where y is -0.0, negative or NaN (torch's threshold_backward passes g at a NaN y).
  * ---------------------------------------------------------------------------------------------- */
 enum wam_dtype { WAM_DT_F32 = 0, WAM_DT_BF16 = 1 };
 
@@ -626,6 +629,9 @@ int wam_ew_relu_mask(int dtype, int64_t n, const void* g1, const void* g2, const
                      void* stream);
 /* NHWC max pooling (k x k window, stride, zero-area padding pad <= k/2, floor output size):
  * y [n, ho, wo, c], idx [n, ho, wo, c] uint8 = window position kh*k+kw | 0x80 if the max is > 0.
+ * Scan order kh*k+kw over the positions inside the image, as torch: the first of equal maxima wins,
+ * a NaN replaces the running maximum (the last NaN wins, bit 7 clear), a window of -inf keeps its
+ * first valid position. k*k <= 127; WAM_ERR_INVALID_ARG when h + 2 pad < k or w + 2 pad < k.
  * Replaces torch max_pool2d_with_indices after the stem ReLU (torchvision ResNet maxpool);
  * WAM_ERR_UNSUPPORTED when c is not a multiple of the 16-byte vector or pointers are unaligned. */
 int wam_ew_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride, int pad,
@@ -640,7 +646,7 @@ int wam_ew_maxpool_nhwc_backward(int dtype, int64_t n, int64_t h, int64_t w, int
  * (NHWC activations viewed as [N*H*W, C]), w the 1x1 convolution's weight as stored, fp32
  * accumulation, one round-to-nearest-even store. Applied to the unrounded accumulator acc:
  *   WAM_PW_TAIL: out = max((acc + bias_a[n]) + (r0[m, n] + bias_b[n]), 0)   r0 = s [M, N], r1 = NULL;
- *                either bias may be NULL (k_add_bias_relu on the accumulator)
+ *                either bias may be NULL (k_add_bias_relu on the accumulator; a NaN sum stays NaN)
  *   WAM_PW_MASK: out = r1[m, n] > 0 ? acc (+ r0[m, n]) : 0                  r1 = y [M, N], r0 = g2 [M, N]
  *                or NULL; biases NULL (k_relu_mask on the accumulator; 0 where y is -0.0 or NaN)
  * mode | WAM_PW_ROUNDED: acc is rounded to bf16 (nearest even) before the epilogue, i.e. the epilogue

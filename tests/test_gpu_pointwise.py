@@ -114,6 +114,29 @@ def test_gpu_pw_tail_matches_float64(K, N, M):
             assert rc == 0
             _check(got, ref, slack, K, "rounded tail K=%d M=%d ba=%s bs=%s cap=%s" % (K, M, use_a, use_s, cap),
                    c["acc"])
+    # the same case with NaN entries in s and a NaN row in x: the forward ReLU passes NaN on (as
+    # torch.relu and the unfused model do), so the output is NaN at exactly the reference's elements
+    # and every other element is held to the bound above
+    g = torch.Generator(device="cuda").manual_seed(7 * K + M)
+    s = torch.where(torch.rand(M, N, device="cuda", generator=g) < 0.03, torch.full_like(c["s"], float("nan")), c["s"])
+    s[0, 0] = float("nan")
+    x = c["x"].clone()
+    x[M // 2] = float("nan")
+    pre = (x.double() @ c["w"].double().t() + c["ba"].double()) + (s.double() + c["bs"].double())
+    nan = torch.isnan(pre)
+    assert bool(nan[M // 2].all()) and bool(nan[0, 0]) and (M < 30 or not bool(nan.all()))
+    fin = lambda t: torch.where(nan, torch.zeros_like(t), t)  # noqa: E731
+    ref = fin(pre).clamp_min(0)
+    slack = fin(x.double().abs() @ c["w"].double().abs().t()) + c["ba"].double().abs() + c["bs"].double().abs() \
+        + fin(s.double().abs())
+    for cap in _caps(M):
+        for mode in (TAIL, TAIL | ROUNDED):
+            rc, got = _run(mode, K, N, M, x, c["w"], c["ba"], c["bs"], s, None, cap)
+            assert rc == 0
+            assert torch.equal(torch.isnan(got), nan), "tail mode %d K=%d M=%d cap=%s: %d NaN outputs, reference %d" % (
+                mode, K, M, cap, int(torch.isnan(got).sum()), int(nan.sum()))
+            _check(fin(got), ref, slack, K, "tail with NaN inputs, mode %d K=%d M=%d cap=%s" % (mode, K, M, cap),
+                   fin(x.double() @ c["w"].double().t()) if mode & ROUNDED else None)
 
 
 @pytest.mark.gpu

@@ -7,6 +7,7 @@
 // bias add, clamp, residual add, threshold_backward). The kernels below fold each chain into
 // ONE pass:
 //   k_bias_act      y = relu?(y + b[c])                        (conv bias + ReLU, in place)
+//                   relu(v) = v < 0 ? 0 : v everywhere below: a NaN activation stays NaN
 //   k_add_bias_relu out = relu(a + ba[c] + s + bs[c])          (bottleneck tail + residual)
 //   k_relu_mask     out = y > 0 ? g : 0                        (ReLU backward)
 //   k_add_relu_mask out = y > 0 ? g1 + g2 : 0                  (gradient fan-in + ReLU backward)
@@ -33,6 +34,17 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
+// forward ReLU: NaN propagates as in torch.relu / clamp_min (fmaxf(NaN, 0) would return 0)
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+// f2bf(relu_f(f)) with the ReLU taken on the rounded pattern: a value below zero (and -0.0) keeps its
+// sign bit through the rounding, so one signed integer max clears it -- the cost of the fmaxf it
+// replaces, where compare + select on the float costs two instructions and a lane mask
+__device__ __forceinline__ uint16_t f2bf_relu(float f) {
+  uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);  // quiet NaN, either sign
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)((uint32_t)max((int32_t)u, 0) >> 16);
+}
 __device__ __forceinline__ void st1(float* p, int64_t i, float v) { p[i] = v; }
 __device__ __forceinline__ void st1(uint16_t* p, int64_t i, float v) { p[i] = f2bf(v); }
 
@@ -45,6 +57,9 @@ struct Vec<float> {
   typedef float4 raw;
   __device__ static void unpack(const raw& r, float (&v)[4]) { v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w; }
   __device__ static raw pack(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
+  __device__ static raw pack_relu(const float (&v)[4]) {
+    return make_float4(relu_f(v[0]), relu_f(v[1]), relu_f(v[2]), relu_f(v[3]));
+  }
 };
 template <>
 struct Vec<uint16_t> {
@@ -62,6 +77,12 @@ struct Vec<uint16_t> {
     uint32_t w[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf(v[2 * k]) | ((uint32_t)f2bf(v[2 * k + 1]) << 16);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  __device__ static raw pack_relu(const float (&v)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf_relu(v[2 * k]) | ((uint32_t)f2bf_relu(v[2 * k + 1]) << 16);
     return make_uint4(w[0], w[1], w[2], w[3]);
   }
 };
@@ -109,11 +130,8 @@ __global__ void __launch_bounds__(kBlk) k_bias_act(int64_t nvec, int64_t C, int6
     Vec<T>::unpack(r[u], v);
     load_bias<T, CH>(b, q * V, C, inner, bv);
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
-      v[k] += bv[k];
-      if (RELU) v[k] = fmaxf(v[k], 0.f);
-    }
-    reinterpret_cast<R*>(y)[q] = Vec<T>::pack(v);
+    for (int k = 0; k < V; ++k) v[k] += bv[k];
+    reinterpret_cast<R*>(y)[q] = RELU ? Vec<T>::pack_relu(v) : Vec<T>::pack(v);
   }
 }
 
@@ -143,8 +161,8 @@ __global__ void __launch_bounds__(kBlk) k_add_bias_relu(int64_t nvec, int64_t C,
     load_bias<T, CH>(ba, q * V, C, inner, b1);
     load_bias<T, CH>(bs, q * V, C, inner, b2);
 #pragma unroll
-    for (int k = 0; k < V; ++k) va[k] = fmaxf((va[k] + b1[k]) + (vs[k] + b2[k]), 0.f);
-    reinterpret_cast<R*>(out)[q] = Vec<T>::pack(va);
+    for (int k = 0; k < V; ++k) va[k] = (va[k] + b1[k]) + (vs[k] + b2[k]);
+    reinterpret_cast<R*>(out)[q] = Vec<T>::pack_relu(va);
   }
 }
 
@@ -191,9 +209,9 @@ __global__ void __launch_bounds__(kBlk) k_ew_scalar(int op, int64_t n, int64_t C
     float v;
     if (op == 0) {  // bias_act: a = y, out = y
       v = ld1(a, i) + (ba ? ld1(ba, c) : 0.f);
-      if (relu) v = fmaxf(v, 0.f);
+      if (relu) v = relu_f(v);
     } else if (op == 1) {  // add_bias_relu
-      v = fmaxf((ld1(a, i) + (ba ? ld1(ba, c) : 0.f)) + (ld1(s, i) + (bs ? ld1(bs, c) : 0.f)), 0.f);
+      v = relu_f((ld1(a, i) + (ba ? ld1(ba, c) : 0.f)) + (ld1(s, i) + (bs ? ld1(bs, c) : 0.f)));
     } else {  // relu mask: a = g1, s = g2 (or null), ba = y
       const float gv = s ? ld1(a, i) + ld1(s, i) : ld1(a, i);
       v = ld1(ba, i) > 0.f ? gv : 0.f;
@@ -492,6 +510,8 @@ int maxpool_bwd(const PoolGeom& g, const void* gy, const void* idx, void* gx, in
 
 inline bool pool_geom(PoolGeom& g, int64_t n, int64_t h, int64_t w, int64_t c, int k, int s, int p) {
   if (n < 0 || h < 1 || w < 1 || c < 1 || k < 1 || k * k > 127 || s < 1 || p < 0 || 2 * p > k) return false;
+  // an image smaller than the window has no output; the division below would round -1 / s up to 0
+  if (h + 2 * p < k || w + 2 * p < k) return false;
   g.n = n, g.h = h, g.w = w, g.c = c, g.k = k, g.s = s, g.p = p;
   g.ho = (h + 2 * p - k) / s + 1;
   g.wo = (w + 2 * p - k) / s + 1;

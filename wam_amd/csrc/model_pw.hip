@@ -45,6 +45,14 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
+// f2bf(f < 0 ? 0 : f): the ReLU as one signed integer max on the rounded pattern (a value below zero
+// keeps its sign bit through the rounding); NaN of either sign stays NaN, where fmaxf(f, 0) returns 0
+__device__ __forceinline__ uint16_t f2bf_relu(float f) {
+  uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)((uint32_t)max((int32_t)u, 0) >> 16);
+}
 __device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 
 __device__ __forceinline__ void unpack8(const uint4& r, float (&v)[8]) {
@@ -59,6 +67,12 @@ __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
   uint32_t w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf(v[2 * k]) | ((uint32_t)f2bf(v[2 * k + 1]) << 16);
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ uint4 pack8_relu(const float (&v)[8]) {
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf_relu(v[2 * k]) | ((uint32_t)f2bf_relu(v[2 * k + 1]) << 16);
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
@@ -178,15 +192,16 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
               float sv[8];
               unpack8(e0[d][j], sv);
 #pragma unroll
-              for (int i = 0; i < 8; ++i) v[i] = fmaxf((v[i] + sb[0][cl + i]) + (sv[i] + sb[1][cl + i]), 0.f);
+              for (int i = 0; i < 8; ++i) v[i] = (v[i] + sb[0][cl + i]) + (sv[i] + sb[1][cl + i]);
+              res[j] = pack8_relu(v);  // NaN propagates, as in k_add_bias_relu (fmaxf would return 0)
             } else {
               float yv[8], gv[8];
               unpack8(e1[d][j], yv);
               if (HAS_G2) unpack8(e0[d][j], gv);
 #pragma unroll
               for (int i = 0; i < 8; ++i) v[i] = yv[i] > 0.f ? (HAS_G2 ? v[i] + gv[i] : v[i]) : 0.f;
+              res[j] = pack8(v);
             }
-            res[j] = pack8(v);
           }
         const int nn = nc + D;
         load_e(nn < NCH ? row + nn * 64 : row_next + (nn - NCH) * 64, e0[d], e1[d]);

@@ -88,7 +88,8 @@ def add_bias_relu(a, ba, s, bs):
 
 
 def relu_mask(g, y, g2=None):
-    """y > 0 ? g (+ g2) : 0 in y's layout."""
+    """y > 0 ? g (+ g2) : 0 in y's layout (made dense: the kernel indexes all operands flat)."""
+    y = _like(y, y)
     g = _like(g, y)
     g2 = None if g2 is None else _like(g2, y)
     out = torch.empty_like(y)

@@ -21,6 +21,7 @@
 #ifndef WAM_HIP_H
 #define WAM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -399,6 +400,43 @@ int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_
  * row has mx = -inf; neither is part of the contract. */
 int wam_peak_normalize(int64_t rows, int64_t len, const float* in, float* out, int32_t* silent, int zero_silent,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Insertion / deletion of voxel WAMs (Eval3DWAM; an addition, the reference evaluates no volumes):
+ * the n_iter + 1 masked reconstructions of every volume in one call. The selection rule, the layout of
+ * coeffs, rank and pos and the pad rule are those of wam_rank_mask_coeffs above, for a 3D plan:
+ * mask m of set s keeps the coefficient at per-item offset k when (rank[s, pos[k]] < thr(m)) !=
+ * (deletion != 0), a pos[k] of -1 or outside [0, rank_len) reading as rank -1; a kept value is
+ * multiplied by 1.0f and a dropped one by 0.0f, the approximation like any other band.
+ * out [sets * (n_iter + 1), *rec_shape] float32: volume s * (n_iter + 1) + m = wam_waverec of set s
+ * masked by m. Two routes compute it, bit-identical to each other:
+ *   route 0: the masked sets are written band-major into the workspace (what wam_rank_mask_coeffs
+ *     writes, over the 1 + 7 * levels bands) and wam_waverec reads them: every 3D plan, any alignment;
+ *   route 1: 3D Haar plans with levels <= 2 and dimensions divisible by 2^levels whose wam_waverec runs
+ *     the fused block kernel (not WAM_PLAN_GENERIC): the threshold is applied as the synthesis loads
+ *     its coefficients, nothing is stored in between and no workspace is read. It needs out 16-byte
+ *     and coeffs and pos 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+/* the route a plan takes by itself: 0 = expansion + wam_waverec (any 3D plan), 1 = fused Haar kernel
+ * (where it applies; the faster one there, profiles/eval3d_kbench.txt). Works on host-only plans;
+ * negative for a NULL or non-3D plan. */
+int    wam_waverec_ranked_route(const wam_plan* plan);
+/* bytes of workspace wam_waverec_ranked needs on `route` (-1: the plan's own): route 1 none; route 0
+ * sets * (n_iter + 1) * wam_plan_coeff_numel floats, rounded up to 16 bytes, followed by
+ * wam_plan_workspace_bytes(plan, sets * (n_iter + 1)). 0 for invalid arguments. */
+size_t wam_waverec_ranked_workspace_bytes(const wam_plan* plan, int64_t sets, int64_t n_iter, int route);
+/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
+ * wam_waverec_ranked_workspace_bytes(plan, sets, n_iter, 0) bytes on route 0, not read on route 1 (may
+ * be NULL). Forcing route 1 on a plan it does not serve, or with pointers it cannot take, returns
+ * WAM_ERR_UNSUPPORTED; with route -1 a call whose pointers route 1 cannot take runs route 0 when a
+ * workspace is given. A non-3D plan: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG as for
+ * wam_rank_mask_coeffs (a NULL plan, coeffs, rank, pos or out, sets < 0, rank_len < 1 or > INT32_MAX,
+ * n_iter < 1, n_comp < 0), for a host-only plan, another route value, more than 65535 * 16 masks, and
+ * for a NULL or misaligned workspace on route 0; nothing is launched then. sets == 0 returns WAM_OK. */
+int    wam_waverec_ranked(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
+                          int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
+                          int route /* -1: the plan's own */, float* out /* [sets*(n_iter+1), *rec_shape] */,
+                          void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * WAMAnalyzer2D (src/analyzers.py:16-203, src/analyzers_helpers.py:6-134): necessary components

@@ -1,4 +1,4 @@
-"""VGPR / SGPR / spill counts of the kernels in one .hip file (compiled for gfx950 with
+"""VGPR / SGPR / spill counts, scratch and LDS bytes and waves per SIMD of the kernels in one .hip file (compiled for gfx950 with
 --save-temps into a temp dir). usage: python scripts/kernel_regs.py wam_amd/csrc/dwt2_plane.hip [regex]"""
 import os
 import re
@@ -18,6 +18,9 @@ for b in re.split(r"\n\s+- \.agpr_count", s):
     if not n or not pat.search(n.group(1)):
         continue
     g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, b) or [None, "?"])[1]
-    print("%-90s vgpr %3s sgpr %3s sgpr_spill %3s vgpr_spill %3s lds %6s" % (
+    # waves per SIMD the unified 512-register file admits (arch + acc VGPRs, allocated in eights; at most 8)
+    regs = int(g("vgpr_count")) if g("vgpr_count") != "?" else 0
+    occ = min(8, 512 // max(8, (regs + 7) // 8 * 8))
+    print("%-90s vgpr %3s sgpr %3s sgpr_spill %3s vgpr_spill %3s scratch %4s lds %6s waves/simd %d" % (
         n.group(1)[:90], g("vgpr_count"), g("sgpr_count"), g("sgpr_spill_count"), g("vgpr_spill_count"),
-        g("group_segment_fixed_size")))
+        g("private_segment_fixed_size"), g("group_segment_fixed_size"), occ))

@@ -15,12 +15,12 @@ from .transforms import wavedec, wavedec2, wavedec3, waverec, waverec2, waverec3
 from .wam_1D import BaseWAM1D, VisualizerWAM1D, WaveletAttribution1D
 from .wam_2D import BaseWAM2D, WaveletAttribution2D
 from .wam_3D import BaseWAM3D, WaveletAttribution3D
-from .evaluation import Eval1DWAM, Eval2DWAM
+from .evaluation import Eval1DWAM, Eval2DWAM, Eval3DWAM
 from .analysis import WAMAnalyzer2D
 from .baselines import EvalImageBaselines, GradCAM, GradCAMPlusPlus, IntegratedGradients, Saliency, SmoothGrad
 from .baselines_audio import EvalAudioBaselines
 
 __all__ = ["WaveletDetailTuple2d", "wavedec", "waverec", "wavedec2", "waverec2", "wavedec3", "waverec3",
            "BaseWAM1D", "WaveletAttribution1D", "VisualizerWAM1D", "BaseWAM2D", "WaveletAttribution2D", "BaseWAM3D",
-           "WaveletAttribution3D", "Eval1DWAM", "Eval2DWAM", "WAMAnalyzer2D", "EvalImageBaselines", "EvalAudioBaselines", "GradCAM",
+           "WaveletAttribution3D", "Eval1DWAM", "Eval2DWAM", "Eval3DWAM", "WAMAnalyzer2D", "EvalImageBaselines", "EvalAudioBaselines", "GradCAM",
            "GradCAMPlusPlus", "SmoothGrad", "Saliency", "IntegratedGradients"]

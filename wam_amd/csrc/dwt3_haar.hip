@@ -8,7 +8,7 @@
 // need 3 passes per level with intermediate volumes in HBM; this is one pass over the data.
 // Arithmetic follows the per-axis kernels exactly (W then H then D; fmaf chains starting at 0),
 // so results are bit-identical to the generic path.
-#include "kernels.hpp"
+#include "maskexpand.hpp"
 #include "rng.hpp"
 
 namespace {
@@ -273,6 +273,120 @@ __global__ void __launch_bounds__(kT3) k_haar3_syn(const float* __restrict__ coe
     }
 }
 
+// Ranked synthesis (wam_waverec_ranked, route 1): k_haar3_syn with the rank threshold of the
+// insertion / deletion masks applied on the load. A thread reads its block's coefficients and,
+// through pos, their ranks once, then walks the chunk of masks blockIdx.y names (kMaskChunk, as the
+// mask expansion of maskexpand.hpp): for mask m every coefficient -- the approximation like any other
+// -- is multiplied by 1.0f or 0.0f ((rank < thr(m)) != deletion, a multiply and not a select: a dropped
+// NaN stays NaN), the levels are inverted in registers and the block goes to output volume
+// item * (n_iter + 1) + m. The arithmetic is the expansion's multiply followed by k_haar3_syn's chains
+// (whose scale is 1.0f there), so the volumes are bit-identical to that two-step route; the
+// (n_iter + 1) masked coefficient sets are never stored.
+template <int J>
+__global__ void __launch_bounds__(kT3) k_haar3_syn_ranked(const float* __restrict__ coeffs,
+                                                         const int32_t* __restrict__ rank, int64_t rank_len,
+                                                         const int32_t* __restrict__ pos, float* __restrict__ out,
+                                                         const float* __restrict__ filt, Haar3Geom g, int64_t blocks,
+                                                         int64_t n_iter, int64_t n_comp, int deletion) {
+  constexpr int B = 1 << J;
+  constexpr int B1 = B / 2;
+  const int64_t t = (int64_t)blockIdx.x * kT3 + threadIdx.x;
+  if (t >= blocks) return;
+  const int64_t bw = g.W / B, bh = g.H / B, bd = g.D / B;
+  const int64_t bx = t % bw, by = (t / bw) % bh, bz = (t / (bw * bh)) % bd, item = t / (bw * bh * bd);
+  const float r[4] = {filt[0], filt[1], filt[2], filt[3]};  // rec lo0 lo1, rec hi0 hi1
+  const int32_t* rk = rank + item * rank_len;
+  const int64_t d1 = g.D / 2, h1 = g.H / 2, w1 = g.W / 2;
+  const int64_t n1 = d1 * h1 * w1;
+  // coarsest level: J = 1 the approximation alone (slot 0 of the level-1 block), J = 2 eight bands
+  float c2[8];
+  int32_t r2[8];
+  float c1[B1][B1][B1][8];
+  int32_t r1[B1][B1][B1][8];
+  if constexpr (J == 1) {
+    const int64_t o = (bz * h1 + by) * w1 + bx;
+    c1[0][0][0][0] = coeffs[g.items * g.off_a + item * n1 + o];
+    r1[0][0][0][0] = slot_rank(rk, pos[g.off_a + o], rank_len);
+  } else {
+    const int64_t h2 = h1 / 2, w2 = w1 / 2, n2 = (d1 / 2) * h2 * w2, o = (bz * h2 + by) * w2 + bx;
+    c2[0] = coeffs[g.items * g.off_a + item * n2 + o];
+    r2[0] = slot_rank(rk, pos[g.off_a + o], rank_len);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+      c2[k] = coeffs[g.items * g.off[1][k - 1] + item * n2 + o];
+      r2[k] = slot_rank(rk, pos[g.off[1][k - 1] + o], rank_len);
+    }
+  }
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    const float* src = coeffs + g.items * g.off[0][k - 1] + item * n1;
+    const int32_t* ps = pos + g.off[0][k - 1];
+#pragma unroll
+    for (int z = 0; z < B1; ++z)
+#pragma unroll
+      for (int y = 0; y < B1; ++y) {
+        const int64_t o = ((bz * B1 + z) * h1 + (by * B1 + y)) * w1 + bx * B1;
+        if constexpr (B1 == 2) {
+          const float2 q = *reinterpret_cast<const float2*>(src + o);
+          const int2 pq = *reinterpret_cast<const int2*>(ps + o);
+          c1[z][y][0][k] = q.x;
+          c1[z][y][1][k] = q.y;
+          r1[z][y][0][k] = slot_rank(rk, pq.x, rank_len);
+          r1[z][y][1][k] = slot_rank(rk, pq.y, rank_len);
+        } else {
+          c1[z][y][0][k] = src[o];
+          r1[z][y][0][k] = slot_rank(rk, ps[o], rank_len);
+        }
+      }
+  }
+  const int64_t M = n_iter + 1, vol = g.D * g.H * g.W;
+  const int64_t m0 = (int64_t)blockIdx.y * kMaskChunk;
+  const int64_t m1 = m0 + kMaskChunk < M ? m0 + kMaskChunk : M;
+  const bool del = deletion != 0;
+  float* dst0 = out + item * M * vol + (bz * B * g.H + by * B) * g.W + bx * B;
+#pragma unroll 1
+  for (int64_t m = m0; m < m1; ++m) {
+    const int32_t thr = (int32_t)mask_thr(m, n_iter, n_comp, rank_len);  // rank_len <= INT32_MAX (host check)
+    auto keep = [&](int32_t rv) { return ((rv < thr) != del) ? 1.f : 0.f; };
+    float ll[B1][B1][B1];
+    if constexpr (J == 1) {
+      ll[0][0][0] = c1[0][0][0][0] * keep(r1[0][0][0][0]);
+    } else {
+      float cm[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cm[k] = c2[k] * keep(r2[k]);
+      haar3_inv(cm, r, ll);
+    }
+    float* dst = dst0 + m * vol;
+#pragma unroll
+    for (int z = 0; z < B1; ++z)
+#pragma unroll
+      for (int y = 0; y < B1; ++y) {
+        float v[2][2][B];  // rows (2z + a, 2y + b) of the block
+#pragma unroll
+        for (int x = 0; x < B1; ++x) {
+          float cm[8], blk[2][2][2];
+          cm[0] = ll[z][y][x];
+#pragma unroll
+          for (int k = 1; k < 8; ++k) cm[k] = c1[z][y][x][k] * keep(r1[z][y][x][k]);
+          haar3_inv(cm, r, blk);
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) v[a][b][2 * x] = blk[a][b][0], v[a][b][2 * x + 1] = blk[a][b][1];
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            float* row = dst + ((int64_t)(2 * z + a) * g.H + (2 * y + b)) * g.W;
+            if constexpr (B == 4) wam_st4(row, v[a][b][0], v[a][b][1], v[a][b][2], v[a][b][3]);
+            else wam_st(reinterpret_cast<wam_f2v*>(row), wam_f2v{v[a][b][0], v[a][b][1]});
+          }
+      }
+  }
+}
+
 Haar3Geom make_geom3(const wam_plan* p, int64_t items) {
   Haar3Geom g{};
   g.J = p->levels;
@@ -360,5 +474,33 @@ int launch_dwt3_haar_synthesis(const wam_plan* p, int64_t batch, const float* co
       hipLaunchKernelGGL(k_haar3_syn<2>, dim3((unsigned)grid), dim3(kT3), 0, st, coeffs, o, filt, g, blocks, s);
     WAM_LAUNCH_CHECK();
   }
+  return WAM_OK;
+}
+
+// The fused route of wam_waverec_ranked. Declines (WAM_ERR_UNSUPPORTED) what the kernel's vector
+// accesses cannot take: out not 16-byte, coeffs or pos not 8-byte aligned.
+int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
+                                      int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp,
+                                      int deletion, float* out, hipStream_t st) {
+  if (!dwt3_haar_supported(p) || !aligned16(out) || ((uintptr_t)coeffs & 7) || ((uintptr_t)pos & 7))
+    return WAM_ERR_UNSUPPORTED;
+  const Haar3Geom g = make_geom3(p, sets);
+  const int B = 1 << p->levels;
+  const int64_t blocks = sets * (g.D / B) * (g.H / B) * (g.W / B);
+  const int64_t grid = (blocks + kT3 - 1) / kT3, M = n_iter + 1, chunks = (M + kMaskChunk - 1) / kMaskChunk;
+  if (grid > 0x7fffffff) return WAM_ERR_UNSUPPORTED;
+  if (chunks > 65535) return WAM_ERR_INVALID_ARG;
+  const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;  // rec lo0 lo1 hi0 hi1
+  const double K = (double)p->band_off[p->nbands];
+  WamTimer tm(st, "k_haar3_syn_ranked",
+              4.0 * (sets * K + (double)sets * rank_len + K + (double)sets * M * g.D * g.H * g.W));
+  const dim3 gd((unsigned)grid, (unsigned)chunks);
+  if (p->levels == 1)
+    hipLaunchKernelGGL(k_haar3_syn_ranked<1>, gd, dim3(kT3), 0, st, coeffs, rank, rank_len, pos, out, filt, g, blocks,
+                       n_iter, n_comp, deletion);
+  else
+    hipLaunchKernelGGL(k_haar3_syn_ranked<2>, gd, dim3(kT3), 0, st, coeffs, rank, rank_len, pos, out, filt, g, blocks,
+                       n_iter, n_comp, deletion);
+  WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

@@ -12,12 +12,7 @@
 namespace {
 
 constexpr int kMaxBands1D = 1 + WAM_MAX_LEVELS;
-using RankBands = MaskBands<kMaxBands1D>;
-
-// a mask slot outside [0, rank_len) is the pad column: rank -1, below every threshold
-__device__ __forceinline__ int32_t slot_rank(const int32_t* __restrict__ rank, int32_t p, int64_t rank_len) {
-  return ((uint64_t)(int64_t)p < (uint64_t)rank_len) ? rank[p] : -1;
-}
+constexpr int kMaxBands3D = WAM_MAX_BANDS;  // 1 + 7 * levels: the expansion of wam_waverec_ranked's route 0
 
 // mask_expand's policy: an element's fate is the rank of its mask slot pos[k] in its set's row.
 // IDENT: the slot of element k is k (wam_rank_mask_rows), pos is not read.
@@ -46,8 +41,9 @@ struct RankPolicy {
   __device__ int64_t out_step() const { return 1; }
 };
 
-template <bool IDENT>
-__global__ void __launch_bounds__(256) k_rank_mask(int64_t sets, RankBands rb, const float* __restrict__ coeffs,
+// CAP: the band table's size, kMaxBands1D for the audio entries, kMaxBands3D for volumes
+template <bool IDENT, int CAP>
+__global__ void __launch_bounds__(256) k_rank_mask(int64_t sets, MaskBands<CAP> rb, const float* __restrict__ coeffs,
                                                    const int32_t* __restrict__ rank, int64_t rank_len,
                                                    const int32_t* __restrict__ pos, int64_t n_iter, int64_t n_comp,
                                                    int deletion, float* __restrict__ out) {
@@ -56,10 +52,11 @@ __global__ void __launch_bounds__(256) k_rank_mask(int64_t sets, RankBands rb, c
               (int64_t)gridDim.x * blockDim.x);
 }
 
+template <int CAP>
 int launch_rank_mask(bool ident, int64_t sets, int nbands, const int64_t* band_off, bool ptrs_aligned,
                      const float* coeffs, const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
                      int64_t n_comp, int deletion, float* out, hipStream_t st, const char* name) {
-  RankBands rb{};
+  MaskBands<CAP> rb{};
   const int64_t units = fill_mask_bands(rb, nbands, band_off, sets, ptrs_aligned);
   if (units == 0) return WAM_OK;
   const int64_t K = rb.off[rb.nbands];
@@ -68,10 +65,10 @@ int launch_rank_mask(bool ident, int64_t sets, int nbands, const int64_t* band_o
   WamTimer tm(st, name, 4.0 * (sets * K + sets * rank_len + (ident ? 0 : K) + (double)sets * M * K));
   const dim3 grid(wam_grid(units, 256), (unsigned)((M + kMaskChunk - 1) / kMaskChunk));
   if (ident)
-    hipLaunchKernelGGL(k_rank_mask<true>, grid, dim3(256), 0, st, sets, rb, coeffs, rank, rank_len, pos, n_iter,
+    hipLaunchKernelGGL((k_rank_mask<true, CAP>), grid, dim3(256), 0, st, sets, rb, coeffs, rank, rank_len, pos, n_iter,
                        n_comp, deletion, out);
   else
-    hipLaunchKernelGGL(k_rank_mask<false>, grid, dim3(256), 0, st, sets, rb, coeffs, rank, rank_len, pos, n_iter,
+    hipLaunchKernelGGL((k_rank_mask<false, CAP>), grid, dim3(256), 0, st, sets, rb, coeffs, rank, rank_len, pos, n_iter,
                        n_comp, deletion, out);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
@@ -122,6 +119,16 @@ __global__ void __launch_bounds__(1024) k_peak_normalize(int64_t len, const floa
 
 }  // namespace
 
+// wam_rank_mask_coeffs's expansion over the bands of a 3D plan (evaluate3d.hip, route 0)
+int launch_rank_mask_coeffs3(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
+                             int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
+                             float* out, hipStream_t st) {
+  if (p->ndim != 3 || p->nbands > kMaxBands3D) return WAM_ERR_UNSUPPORTED;
+  const bool ptrs_aligned = aligned16(coeffs) && aligned16(pos) && aligned16(out);
+  return launch_rank_mask<kMaxBands3D>(false, sets, p->nbands, p->band_off, ptrs_aligned, coeffs, rank, rank_len, pos,
+                                       n_iter, n_comp, deletion, out, st, "k_rank_mask_coeffs3");
+}
+
 extern "C" {
 
 int wam_rank_mask_coeffs(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
@@ -132,8 +139,8 @@ int wam_rank_mask_coeffs(const wam_plan* plan, int64_t sets, const float* coeffs
   if (plan->ndim != 1 || plan->nbands > kMaxBands1D) return WAM_ERR_UNSUPPORTED;
   if (rank_len > INT32_MAX) return WAM_ERR_INVALID_ARG;
   const bool ptrs_aligned = aligned16(coeffs) && aligned16(pos) && aligned16(out);
-  return launch_rank_mask(false, sets, plan->nbands, plan->band_off, ptrs_aligned, coeffs, rank, rank_len, pos, n_iter,
-                          n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_coeffs");
+  return launch_rank_mask<kMaxBands1D>(false, sets, plan->nbands, plan->band_off, ptrs_aligned, coeffs, rank, rank_len,
+                                       pos, n_iter, n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_coeffs");
 }
 
 int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_t* rank, int64_t n_iter,
@@ -141,8 +148,9 @@ int wam_rank_mask_rows(int64_t sets, int64_t len, const float* src, const int32_
   if (sets < 0 || len < 1 || len > INT32_MAX || n_iter < 1 || n_comp < 0 || !src || !rank || !out)
     return WAM_ERR_INVALID_ARG;
   const int64_t band_off[2] = {0, len};
-  return launch_rank_mask(true, sets, 1, band_off, aligned16(src) && aligned16(rank) && aligned16(out), src, rank, len,
-                          nullptr, n_iter, n_comp, deletion, out, (hipStream_t)stream, "k_rank_mask_rows");
+  return launch_rank_mask<kMaxBands1D>(true, sets, 1, band_off, aligned16(src) && aligned16(rank) && aligned16(out), src,
+                                       rank, len, nullptr, n_iter, n_comp, deletion, out, (hipStream_t)stream,
+                                       "k_rank_mask_rows");
 }
 
 int wam_peak_normalize(int64_t rows, int64_t len, const float* in, float* out, int32_t* silent, int zero_silent,

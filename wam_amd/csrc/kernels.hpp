@@ -185,3 +185,13 @@ int launch_dwt3_haar_analysis_noisy(const wam_plan* p, int64_t batch, const floa
                                     const WamNoise* nz, int64_t n_samples, hipStream_t st);
 int launch_dwt3_haar_synthesis(const wam_plan* p, int64_t batch, const float* coeffs, const float* alpha, int n_alpha,
                                float* out, hipStream_t st);
+
+// wam_waverec_ranked (evaluate3d.hip). Route 1: the rank threshold applied on the synthesis load
+// (dwt3_haar.hip), out = sets * (n_iter + 1) volumes, nothing in between. Route 0's first half: the
+// masked coefficient sets through the shared mask_expand skeleton (evaluate1d.hip), any 3D plan.
+int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
+                                      int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp,
+                                      int deletion, float* out, hipStream_t st);
+int launch_rank_mask_coeffs3(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
+                             int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
+                             float* out, hipStream_t st);

@@ -19,6 +19,12 @@ __device__ __forceinline__ int64_t mask_thr(int64_t m, int64_t n_iter, int64_t n
   return t < len ? t : len;
 }
 
+// the rank of mask slot p in a set's rank row; a slot outside [0, rank_len) is the pad column: rank -1,
+// below every threshold
+__device__ __forceinline__ int32_t slot_rank(const int32_t* __restrict__ rank, int32_t p, int64_t rank_len) {
+  return ((uint64_t)(int64_t)p < (uint64_t)rank_len) ? rank[p] : -1;
+}
+
 template <int CAP>
 struct MaskBands {
   int nbands;

@@ -48,6 +48,7 @@ from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, chec
                        class_curves, class_probs, coeff_array_layout, compute_auc, db_melspec, descending_ranks,
                        device_table, generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, rank_mask_rows,
                        resize_default, show_images, softmax, zoom_cell_map)
+from .evaluation3d import Eval3DWAM  # noqa: F401  (the volume evaluator, an addition: its own module)
 from .plan import get_plan
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d

@@ -121,30 +121,36 @@ def mosaic_map(plan, canvas_hw, base_hw, device):
     return _CACHE[key]
 
 
+def cube_index(plan, input_size):
+    """cube_map on the host: int64 [S, S, S], the per-item coefficient offset behind every cube voxel
+    (-1: none). `plan` needs levels, band_shapes and band_offsets only."""
+    S = int(input_size)
+    J = plan.levels
+    src = np.full((S, S, S), -1, dtype=np.int64)
+    idx = [int(S / 2 ** j) for j in range(J + 1)][::-1]
+    idx.insert(0, 0)
+    for i in range(J + 1):
+        s, e = idx[i], idx[i + 1]
+        if s == 0:
+            src[:e, :e, :e] = _band_index(plan, 0)
+        else:
+            b0 = 1 + (i - 1) * 7  # coeffs[i] = details of level J-i+1, ptwt key order aad..ddd
+            keys = ["aad", "ada", "add", "daa", "dad", "dda", "ddd"]
+            lv = {k: _band_index(plan, b0 + n) for n, k in enumerate(keys)}
+            src[s:e, s:e, s:e] = lv["ddd"]
+            src[:s, :s, s:e] = lv["aad"]
+            src[:s, s:e, :s] = lv["ada"]
+            src[:s, s:e, s:e] = lv["add"]
+            src[s:e, :s, :s] = lv["daa"]
+            src[s:e, :s, s:e] = lv["dad"]
+            src[s:e, s:e, :s] = lv["dda"]
+    return src
+
+
 def cube_map(plan, input_size, device):
     """BaseWAM3D.refactor (lib/wam_3D.py:127-166) as a gather map over item-major |g| maps.
     ``input_size`` is the refactor's cube size (the reference's self.input_size)."""
     key = ("cube", plan, int(input_size))
     if key not in _CACHE:
-        S = int(input_size)
-        J = plan.levels
-        src = np.full((S, S, S), -1, dtype=np.int64)
-        idx = [int(S / 2 ** j) for j in range(J + 1)][::-1]
-        idx.insert(0, 0)
-        for i in range(J + 1):
-            s, e = idx[i], idx[i + 1]
-            if s == 0:
-                src[:e, :e, :e] = _band_index(plan, 0)
-            else:
-                b0 = 1 + (i - 1) * 7  # coeffs[i] = details of level J-i+1, ptwt key order aad..ddd
-                keys = ["aad", "ada", "add", "daa", "dad", "dda", "ddd"]
-                lv = {k: _band_index(plan, b0 + n) for n, k in enumerate(keys)}
-                src[s:e, s:e, s:e] = lv["ddd"]
-                src[:s, :s, s:e] = lv["aad"]
-                src[:s, s:e, :s] = lv["ada"]
-                src[:s, s:e, s:e] = lv["add"]
-                src[s:e, :s, :s] = lv["daa"]
-                src[s:e, :s, s:e] = lv["dad"]
-                src[s:e, s:e, :s] = lv["dda"]
-        _CACHE[key] = torch.as_tensor(src.reshape(-1).astype(np.int32)).to(device)
+        _CACHE[key] = torch.as_tensor(cube_index(plan, input_size).reshape(-1).astype(np.int32)).to(device)
     return _CACHE[key]

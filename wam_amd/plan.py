@@ -110,6 +110,41 @@ class Plan:
                               stream_of(flat.device)))
         return out
 
+    @property
+    def ranked_route(self):
+        """The route waverec_ranked takes by itself (wam_waverec_ranked_route): 0 = mask expansion +
+        waverec, 1 = the fused 3D Haar kernel. 3D plans only."""
+        r = lib.wam_waverec_ranked_route(self._h)
+        if r < 0:
+            check(-r)
+        return r
+
+    def waverec_ranked(self, flat, sets, rank, pos, n_iter, n_comp, deletion, route=-1, out=None):
+        """The n_iter + 1 masked reconstructions of each of `sets` volumes (wam_waverec_ranked): flat
+        band-major coefficients of the sets, rank int32 [sets, rank_len] and pos int32 [coeff_numel] as
+        for wam_rank_mask_coeffs -> [sets * (n_iter + 1), *rec_shape], volume s * (n_iter + 1) + m.
+        route: -1 the plan's own, 0 expansion + waverec (workspace from the plan), 1 the fused kernel."""
+        require_cuda(flat, "coefficients")
+        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
+        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise TypeError("wam_amd: rank and pos must be int32")
+        if flat.numel() != sets * self.coeff_numel or pos.numel() != self.coeff_numel or rank.shape[0] != sets:
+            raise ValueError("expected %d x %d coefficients, %d positions and %d rank rows"
+                             % (sets, self.coeff_numel, self.coeff_numel, sets))
+        M = int(n_iter) + 1
+        if out is None:
+            out = torch.empty((sets * M,) + self.rec_shape, dtype=torch.float32, device=flat.device)
+        ws = None
+        # the plan's own route keeps a workspace at hand only when it is route 0
+        n = int(lib.wam_waverec_ranked_workspace_bytes(self._h, sets, n_iter, route))
+        if n:
+            ws = self._ws.get("ranked")
+            if ws is None or ws.numel() < n:
+                ws = self._ws["ranked"] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib.wam_waverec_ranked(self._h, sets, ptr(flat), ptr(rank), rank.shape[1], ptr(pos), n_iter, n_comp,
+                                     int(bool(deletion)), route, ptr(out), ptr(ws), stream_of(flat.device)))
+        return out
+
     def waverec_bf16_nhwc(self, flat, batch, channels, alphas=None, out=None):
         """flat band-major coefficients of `batch` planes (images x channels) -> the reconstruction as
         bf16 images [n_alpha * batch / channels, channels, *rec_shape] in channels_last memory (the

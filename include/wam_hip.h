@@ -439,6 +439,52 @@ int    wam_waverec_ranked(const wam_plan* plan, int64_t sets, const float* coeff
                           void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Insertion / deletion of image WAMs by ranking (Eval2DWAM with mask_layout="mosaic"): the
+ * n_iter + 1 masked reconstructions of every image's channel planes in one call. wam_waverec_ranked
+ * above stays 3D-only; these are the entries of 2D plans. The selection rule is wam_rank_mask_coeffs's:
+ * thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len; mask m of image n keeps the
+ * coefficient at per-plane offset k when (rank[n, pos[k]] < thr(m)) != (deletion != 0), a pos[k] of -1
+ * or outside [0, rank_len) reading as rank -1; a kept value is multiplied by 1.0f and a dropped one by
+ * 0.0f (a dropped negative value is -0.0f, a dropped NaN stays NaN), the approximation like any band.
+ * coeffs: band-major coefficients of images * channels planes as wam_wavedec writes them, plane (n, c)
+ * = n * channels + c (wam_threshold_mask_coeffs's layout). rank [images, rank_len] int32 (device), one
+ * ranking per image shared by its channels. pos [K] int32 (device), K = wam_plan_coeff_numel, shared by
+ * all planes. out [images, n_iter + 1, channels, rec_h, rec_w] float32: image n, mask m is a contiguous
+ * [channels, rec_h, rec_w] block. Two routes compute it, bit-identical to each other:
+ *   route 0: the masked sets are written band-major into the workspace (planes (n, m, c), the mask
+ *     expansion of wam_rank_mask_coeffs over the 1 + 3 * levels bands) and wam_waverec reads them,
+ *     whatever route the plan's synthesis takes: every 2D plan, any alignment of coeffs, pos and out;
+ *   route 1: plans whose wam_waverec runs the plane-resident synthesis (filters up to 8 taps whose
+ *     levels fit its LDS, not WAM_PLAN_GENERIC / WAM_PLAN_NO_PLANE): a pre-pass writes the ranking in
+ *     coefficient order once per image (images * K int32 of workspace), and the synthesis applies the
+ *     threshold as it loads its coefficient rows; no masked coefficient is stored. It needs out 8-byte
+ *     aligned (its pixel pairs are 8-byte stores); coeffs, rank and pos need only their natural 4.
+ * ---------------------------------------------------------------------------------------------- */
+/* the route a plan takes by itself: 0 = expansion + wam_waverec, 1 = the fused plane-resident kernel
+ * (only where it measured faster, profiles/eval2d_kbench.txt). Works on host-only plans; negative for
+ * a NULL or non-2D plan. */
+int    wam_waverec2_ranked_route(const wam_plan* plan);
+/* bytes of workspace wam_waverec2_ranked needs on `route`: route 1 the rank table, images * K int32
+ * rounded up to 16 bytes; route 0 images * (n_iter + 1) * channels * K floats, rounded up to 16 bytes,
+ * followed by wam_plan_workspace_bytes(plan, images * (n_iter + 1) * channels); -1 (the plan's own)
+ * route 0's size, which is the fallback's and holds route 1's table too. 0 for invalid arguments. */
+size_t wam_waverec2_ranked_workspace_bytes(const wam_plan* plan, int64_t images, int channels, int64_t n_iter,
+                                           int route);
+/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
+ * wam_waverec2_ranked_workspace_bytes(plan, images, channels, n_iter, route) bytes. Forcing route 1 on a
+ * plan it does not serve, or with an `out` it cannot take, returns WAM_ERR_UNSUPPORTED; with route -1 a
+ * call whose pointers route 1 cannot take runs route 0. A non-2D plan: WAM_ERR_UNSUPPORTED.
+ * WAM_ERR_INVALID_ARG: a NULL plan, coeffs, rank, pos or out, images < 0, channels outside 1..4,
+ * rank_len < 1 or > INT32_MAX, n_iter < 1, n_comp < 0, a host-only plan, another route value, a NULL or
+ * misaligned workspace, more than 65535 * 16 masks on route 0 or more than INT32_MAX (plane, mask)
+ * pairs on route 1; nothing is launched then. images == 0 returns WAM_OK. */
+int    wam_waverec2_ranked(const wam_plan* plan, int64_t images, int channels, const float* coeffs,
+                           const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
+                           int64_t n_comp, int deletion, int route /* -1: the plan's own */,
+                           float* out /* [images, n_iter+1, channels, rec_h, rec_w] */, void* workspace,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * WAMAnalyzer2D (src/analyzers.py:16-203, src/analyzers_helpers.py:6-134): necessary components
  * (quantile thresholds on the WAM map) and scale isolation (one mask per level). The reference's
  * per-image, per-quantile CPU loop (3 x pywt.wavedec2 -> coeffs_to_array -> arr * (grad_wam >= t) ->

@@ -948,6 +948,84 @@ __global__ void __launch_bounds__(kPT) __attribute__((amdgpu_waves_per_eu(4, 8))
   }
 }
 
+// Ranked synthesis (wam_waverec2_ranked, route 1): k_plane_syn at scale 1.0f with the rank threshold
+// of the mask expansion applied as syn_stream's coefficient rows enter its ring (SynKeepRank), so
+// the M = n_iter + 1 masked coefficient sets of a plane are never written. One workgroup per (plane,
+// mask), mask-fastest: the masks of one plane share an XCD, its coefficient reads and its rank reads.
+// rtab [images, K] int32: the rank of every coefficient's mask slot in coefficient order (k_rank_table),
+// read at the coefficient's own offset. out [images, M, channels, oh, ow], plane = image * channels +
+// channel. g.batch = planes, g.n_alpha = M.
+struct RankedArgs {
+  const int32_t* rtab;
+  int64_t K, rank_len, n_iter, n_comp;
+  int channels, deletion;
+};
+
+__global__ void __launch_bounds__(256) k_rank_table(int64_t images, int64_t K, const int32_t* __restrict__ rank,
+                                                    int64_t rank_len, const int32_t* __restrict__ pos,
+                                                    int32_t* __restrict__ rtab) {
+  const int64_t total = images * K;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = t / K;
+    const int32_t p = pos[t - n * K];
+    rtab[t] = ((uint64_t)(int64_t)p < (uint64_t)rank_len) ? rank[n * rank_len + p] : -1;
+  }
+}
+
+template <int L>
+__global__ void __launch_bounds__(kPT) __attribute__((amdgpu_waves_per_eu(4, 8)))
+    k_plane_syn_ranked(const float* __restrict__ coeffs, float* __restrict__ out, const float* __restrict__ filt,
+                       SynGeom g, RankedArgs ra, int64_t n_items) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int64_t nwg = gridDim.x, bid = blockIdx.x;
+  const int64_t q8 = nwg / 8, r8 = nwg % 8, xcd = bid % 8;
+  const int64_t lwg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  if (lwg >= n_items) return;  // never taken (grid == n_items)
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t item = lwg / g.n_alpha;  // the plane
+  const int64_t m = lwg % g.n_alpha;     // the mask
+  const int64_t image = item / ra.channels;
+  // thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len (maskexpand.hpp mask_thr)
+  int64_t thr = m * ra.n_comp;
+  if (m >= ra.n_iter || thr > ra.rank_len) thr = ra.rank_len;
+  if (m == 0) thr = 0;
+  const int32_t* rk = ra.rtab + image * ra.K;
+  float rlo[L], rhi[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    rlo[k] = filt[k];
+    rhi[k] = filt[L + k];
+  }
+  float* bufL = smem;
+  float* bufS = smem + g.lcap;
+  float4* xch = reinterpret_cast<float4*>(smem + g.lcap + g.scap) + wv * 64;
+  for (int l = g.J - 1; l >= 0; --l) {
+    if (l < g.J - 1) __syncthreads();  // LL'_{l+1} complete
+    const int mh = g.mh[l], mw = g.mw[l], oh = g.oh[l], ow = g.ow[l];
+    const int64_t bn = (int64_t)mh * mw;
+    const float* pH = coeffs + g.batch * g.off[l][0] + item * bn;
+    const float* pV = coeffs + g.batch * g.off[l][1] + item * bn;
+    const float* pD = coeffs + g.batch * g.off[l][2] + item * bn;
+    int strip, qbeg, qend;
+    if (!syn_work<L>(oh, ow, wv, strip, qbeg, qend)) continue;
+    float* dst = l == 0 ? out + ((image * g.n_alpha + m) * ra.channels + item % ra.channels) * ((int64_t)oh * ow)
+                        : ((l & 1) ? bufL : bufS);
+    if (l == g.J - 1) {
+      const SynKeepRank<true> kp{rk + g.off_a, rk + g.off[l][0], rk + g.off[l][1], rk + g.off[l][2], thr,
+                                 ra.deletion != 0};
+      syn_stream_to<L, kSynPF, false, SynOutF32, SynKeepRank<true>>(coeffs + g.batch * g.off_a + item * bn, 1.f, pH, pV,
+                                                                    pD, 1.f, mh, mw, SynOutF32{dst}, oh, ow, strip,
+                                                                    qbeg, qend, xch, rlo, rhi, lane, true, kp);
+    } else {
+      const SynKeepRank<false> kp{nullptr, rk + g.off[l][0], rk + g.off[l][1], rk + g.off[l][2], thr,
+                                  ra.deletion != 0};
+      syn_stream_to<L, kSynPF, false, SynOutF32, SynKeepRank<false>>((l & 1) ? bufS : bufL, 1.f, pH, pV, pD, 1.f, mh,
+                                                                     mw, SynOutF32{dst}, oh, ow, strip, qbeg, qend,
+                                                                     xch, rlo, rhi, lane, true, kp);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // filters up to 8 taps (haar, db2-db4, sym2-sym4, coif1): longer filters keep the per-level kernels,
 // whose register ring of L rows x 2 columns x lo/hi does not fit the 128-VGPR budget of 16 waves/CU
@@ -1184,6 +1262,32 @@ bool syn_ok(const wam_plan* p) {
   return (int64_t)syn_lds_floats(p, lcap, scap) * 4 <= kPlaneLdsCap;
 }
 
+SynGeom make_syn_geom(const wam_plan* p, int64_t batch) {
+  SynGeom g{};
+  g.J = p->levels;
+  for (int l = 0; l < p->levels; ++l) {
+    g.mh[l] = (int)p->lout[l][0];
+    g.mw[l] = (int)p->lout[l][1];
+    g.oh[l] = (int)(l ? p->lout[l - 1][0] : p->rec_shape[0]);
+    g.ow[l] = (int)(l ? p->lout[l - 1][1] : p->rec_shape[1]);
+    for (int k = 0; k < 3; ++k) g.off[l][k] = p->band_off[wam_band_of(p, l, k)];
+  }
+  g.off_a = p->band_off[0];
+  g.batch = batch;
+  return g;
+}
+
+template <int L>
+int launch_syn_ranked_t(const SynGeom& g, int lds_bytes, int64_t n_items, const float* coeffs, float* out,
+                        const float* filt, const RankedArgs& ra, double bytes, hipStream_t st) {
+  auto kern = k_plane_syn_ranked<L>;
+  if (int rc = wam_lds_opt_in((const void*)kern, kPlaneLdsCap)) return rc;
+  WamTimer tm(st, "k_plane_syn_ranked", bytes);
+  hipLaunchKernelGGL(kern, dim3((unsigned)n_items), dim3(kPT), lds_bytes, st, coeffs, out, filt, g, ra, n_items);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
 template <int L, int OC>
 int launch_syn_plane_t(const SynGeom& g, int lds_bytes, int64_t n_items, const float* coeffs, void* out,
                        const float* filt, const SynAlphas& al, double bytes, hipStream_t st) {
@@ -1216,17 +1320,7 @@ int launch_dwt2_plane_synthesis(const wam_plan* p, int64_t batch, const float* c
   if (!syn_ok(p)) return WAM_ERR_UNSUPPORTED;
   if (out_channels != 0 && (out_channels != 1 && out_channels != 3)) return WAM_ERR_UNSUPPORTED;
   if (out_channels && batch % out_channels) return WAM_ERR_INVALID_ARG;
-  SynGeom g{};
-  g.J = p->levels;
-  for (int l = 0; l < p->levels; ++l) {
-    g.mh[l] = (int)p->lout[l][0];
-    g.mw[l] = (int)p->lout[l][1];
-    g.oh[l] = (int)(l ? p->lout[l - 1][0] : p->rec_shape[0]);
-    g.ow[l] = (int)(l ? p->lout[l - 1][1] : p->rec_shape[1]);
-    for (int k = 0; k < 3; ++k) g.off[l][k] = p->band_off[wam_band_of(p, l, k)];
-  }
-  g.off_a = p->band_off[0];
-  g.batch = batch;
+  SynGeom g = make_syn_geom(p, batch);
   const int lds_bytes = syn_lds_floats(p, g.lcap, g.scap) * 4;
   const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;
   const double out_item = (double)p->rec_shape[0] * p->rec_shape[1];
@@ -1246,4 +1340,41 @@ int launch_dwt2_plane_synthesis(const wam_plan* p, int64_t batch, const float* c
     if (rc) return rc;
   }
   return WAM_OK;
+}
+
+// The fused route of wam_waverec2_ranked: the rank table in coefficient order (rtab, images * K
+// int32 of the caller's workspace), then one (plane, mask) workgroup each. Declines
+// (WAM_ERR_UNSUPPORTED) a plan k_plane_syn does not serve and pointers its accesses cannot take: the
+// float2 output stores want `out` 8-byte aligned.
+int64_t dwt2_plane_ranked_table_bytes(const wam_plan* p, int64_t images) {
+  return (images * p->band_off[p->nbands] * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;
+}
+
+int launch_dwt2_plane_synthesis_ranked(const wam_plan* p, int64_t images, int channels, const float* coeffs,
+                                       const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
+                                       int64_t n_comp, int deletion, float* out, int32_t* rtab, hipStream_t st) {
+  if (!syn_ok(p) || ((uintptr_t)out & 7) || !rtab || ((uintptr_t)rtab & 3)) return WAM_ERR_UNSUPPORTED;
+  const int64_t planes = images * channels, M = n_iter + 1, K = p->band_off[p->nbands];
+  if (M > INT32_MAX || planes > INT32_MAX / M) return WAM_ERR_INVALID_ARG;  // one workgroup per (plane, mask)
+  SynGeom g = make_syn_geom(p, planes);
+  g.n_alpha = (int)M;
+  const int lds_bytes = syn_lds_floats(p, g.lcap, g.scap) * 4;
+  {
+    WamTimer tm(st, "k_rank_table", 4.0 * (images * (double)rank_len + K + 2.0 * images * K));
+    hipLaunchKernelGGL(k_rank_table, dim3(wam_grid(images * K, 256)), dim3(256), 0, st, images, K, rank, rank_len, pos,
+                       rtab);
+    WAM_LAUNCH_CHECK();
+  }
+  const RankedArgs ra{rtab, K, rank_len, n_iter, n_comp, channels, deletion};
+  const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;
+  // algorithmic bytes: coefficients and ranks once, every reconstruction once
+  const double bytes = 4.0 * ((double)planes * K + (double)images * K +
+                              (double)planes * M * p->rec_shape[0] * p->rec_shape[1]);
+  switch (p->L) {
+    case 2: return launch_syn_ranked_t<2>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
+    case 4: return launch_syn_ranked_t<4>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
+    case 6: return launch_syn_ranked_t<6>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
+    case 8: return launch_syn_ranked_t<8>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
+    default: return WAM_ERR_UNSUPPORTED;
+  }
 }

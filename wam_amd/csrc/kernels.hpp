@@ -195,3 +195,11 @@ int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const flo
 int launch_rank_mask_coeffs3(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
                              int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
                              float* out, hipStream_t st);
+
+// wam_waverec2_ranked (evaluate2d.hip), route 1: k_plane_syn with the rank threshold applied as the
+// coefficient rows are loaded (dwt2_plane.hip). rtab: dwt2_plane_ranked_table_bytes of workspace, the
+// ranks in coefficient order. out [images, n_iter + 1, channels, rec_h, rec_w].
+int64_t dwt2_plane_ranked_table_bytes(const wam_plan* p, int64_t images);
+int launch_dwt2_plane_synthesis_ranked(const wam_plan* p, int64_t images, int channels, const float* coeffs,
+                                       const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
+                                       int64_t n_comp, int deletion, float* out, int32_t* rtab, hipStream_t st);

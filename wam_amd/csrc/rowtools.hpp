@@ -3,6 +3,7 @@
 // loads into registers, committed to a wave-private LDS row whose pad slots carry the boundary
 // extension, filtered horizontally from LDS.
 #pragma once
+#include <type_traits>
 #include "kernels.hpp"
 #include "rng.hpp"
 
@@ -216,12 +217,50 @@ struct SynOutBf16 {
   }
 };
 
-template <int L, int PF = kSynPF, bool PK = (L >= 12), class Out = SynOutF32>
+// Per-coefficient factors of syn_stream: what a fetched coefficient is multiplied by when it enters
+// the ring. SynKeepAll (every caller but the ranked synthesis): nothing is loaded and nothing is
+// multiplied. SynKeepRank (k_plane_syn_ranked, dwt2_plane.hip): the coefficient's rank, read at the
+// coefficient's own offset from a table in coefficient order, against the mask's threshold -- the
+// 1.0f / 0.0f multiply of wam_rank_mask_coeffs. KA: the approximation rows are coefficients too (the
+// coarsest level); elsewhere they are the previous level's output and pass unchanged.
+struct SynKeepAll {
+  struct Rk {};
+  __device__ __forceinline__ void load(unsigned, Rk&, Rk&, Rk&, Rk&) const {}
+  __device__ __forceinline__ float a(float x, Rk) const { return x; }
+  __device__ __forceinline__ float d(float x, Rk) const { return x; }
+};
+
+template <bool KA>
+struct SynKeepRank {
+  using Rk = int32_t;
+  const int32_t* rA;  // rank rows of the four bands, indexed like the bands themselves
+  const int32_t* rH;
+  const int32_t* rV;
+  const int32_t* rD;
+  int64_t thr;
+  bool del;
+  __device__ __forceinline__ void load(unsigned o, Rk& ka, Rk& kh, Rk& kv, Rk& kd) const {
+    ka = KA ? *rk32(rA, o) : 0;
+    kh = *rk32(rH, o);
+    kv = *rk32(rV, o);
+    kd = *rk32(rD, o);
+  }
+  // a 32-bit byte offset from a wave-uniform base, as at32
+  static __device__ __forceinline__ const int32_t* rk32(const int32_t* base, unsigned idx) {
+    return reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(base) + idx * 4u);
+  }
+  __device__ __forceinline__ float keep(Rk rk) const { return (((int64_t)rk < thr) != del) ? 1.f : 0.f; }
+  __device__ __forceinline__ float a(float x, Rk rk) const { return KA ? x * keep(rk) : x; }
+  __device__ __forceinline__ float d(float x, Rk rk) const { return x * keep(rk); }
+};
+
+template <int L, int PF = kSynPF, bool PK = (L >= 12), class Out = SynOutF32, class Keep = SynKeepAll>
 __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, float sa, const float* __restrict__ pH,
                                               const float* __restrict__ pV, const float* __restrict__ pD, float sd,
                                               int mh, int mw, const Out dst, int oh, int ow, int strip,
                                               int qbeg, int qend, float4* xch, const float (&rlo)[L],
-                                              const float (&rhi)[L], int lane, bool vec2 = true) {
+                                              const float (&rhi)[L], int lane, bool vec2 = true,
+                                              const Keep kp = Keep{}) {
   constexpr int p = L - 2;
   constexpr int H2 = L / 2;
   constexpr int OUTQ = 65 - H2;
@@ -233,6 +272,9 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
   const int ucol = 2 * (jj - qs);
   // raw fetched rows (a, h, v, d) + validity; scaled / zeroed when they enter the ring
   float fa[PF], fh[PF], fv[PF], fd[PF];
+  // what decides their factors, fetched beside them (nothing when every coefficient is kept)
+  constexpr bool KEEP = !std::is_same<Keep, SynKeepAll>::value;
+  typename Keep::Rk ka[PF], kh[PF], kv[PF], kd[PF];
   bool fok[PF];
   auto fetch = [&](int u, int q) {
     fok[u] = colv && q >= 0 && q < mh;
@@ -243,7 +285,13 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
     fh[u] = *at32(pH, o);
     fv[u] = *at32(pV, o);
     fd[u] = *at32(pD, o);
+    if constexpr (KEEP) kp.load(o, ka[u], kh[u], kv[u], kd[u]);
   };
+  // a fetched value as it enters the ring
+  auto ca = [&](int u) -> float { if constexpr (KEEP) return kp.a(fa[u], ka[u]); else return fa[u]; };
+  auto ch = [&](int u) -> float { if constexpr (KEEP) return kp.d(fh[u], kh[u]); else return fh[u]; };
+  auto cv = [&](int u) -> float { if constexpr (KEEP) return kp.d(fv[u], kv[u]); else return fv[u]; };
+  auto cd = [&](int u) -> float { if constexpr (KEEP) return kp.d(fd[u], kd[u]); else return fd[u]; };
   if constexpr (PK) {
     // filter pairs (taps 2 i2, 2 i2 + 1): the two outputs of a phase pair as one (packed) chain
     // pair, every output keeping the scalar chain's tap order (same sums)
@@ -259,10 +307,10 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
   #pragma unroll
     for (int k = 0; k < H2 - 1; ++k) {
       fetch(0, qbeg - (H2 - 1) + k);
-      ra[k] = fok[0] ? sa * fa[0] : 0.f;
-      rh[k] = fok[0] ? sd * fh[0] : 0.f;
-      rv[k] = fok[0] ? sd * fv[0] : 0.f;
-      rd[k] = fok[0] ? sd * fd[0] : 0.f;
+      ra[k] = fok[0] ? sa * ca(0) : 0.f;
+      rh[k] = fok[0] ? sd * ch(0) : 0.f;
+      rv[k] = fok[0] ? sd * cv(0) : 0.f;
+      rd[k] = fok[0] ? sd * cd(0) : 0.f;
     }
   #pragma unroll
     for (int u = 0; u < PF; ++u) fetch(u, qbeg + u);
@@ -275,10 +323,10 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
         if (q >= qend) break;  // uniform
         const int uf = u % PF;
         const int ns = (H2 - 1 + u) % H2;  // slot of row q
-        ra[ns] = fok[uf] ? sa * fa[uf] : 0.f;
-        rh[ns] = fok[uf] ? sd * fh[uf] : 0.f;
-        rv[ns] = fok[uf] ? sd * fv[uf] : 0.f;
-        rd[ns] = fok[uf] ? sd * fd[uf] : 0.f;
+        ra[ns] = fok[uf] ? sa * ca(uf) : 0.f;
+        rh[ns] = fok[uf] ? sd * ch(uf) : 0.f;
+        rv[ns] = fok[uf] ? sd * cv(uf) : 0.f;
+        rd[ns] = fok[uf] ? sd * cd(uf) : 0.f;
         // rows past the chunk are never used: re-fetch the chunk's last row (a cache hit) rather
         // than the next chunk's first rows, which that chunk's wave read long ago (HBM re-reads)
         fetch(uf, min(q + PF, qend - 1));
@@ -342,10 +390,10 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
   #pragma unroll
     for (int k = 0; k < H2 - 1; ++k) {
       fetch(0, qbeg - (H2 - 1) + k);
-      ra[k] = fok[0] ? sa * fa[0] : 0.f;
-      rh[k] = fok[0] ? sd * fh[0] : 0.f;
-      rv[k] = fok[0] ? sd * fv[0] : 0.f;
-      rd[k] = fok[0] ? sd * fd[0] : 0.f;
+      ra[k] = fok[0] ? sa * ca(0) : 0.f;
+      rh[k] = fok[0] ? sd * ch(0) : 0.f;
+      rv[k] = fok[0] ? sd * cv(0) : 0.f;
+      rd[k] = fok[0] ? sd * cd(0) : 0.f;
     }
   #pragma unroll
     for (int u = 0; u < PF; ++u) fetch(u, qbeg + u);
@@ -353,10 +401,10 @@ __device__ __forceinline__ void syn_stream_to(const float* __restrict__ pA, floa
   #pragma unroll
       for (int u = 0; u < PF; ++u) {
         const int q = base + u;
-        ra[H2 - 1] = fok[u] ? sa * fa[u] : 0.f;
-        rh[H2 - 1] = fok[u] ? sd * fh[u] : 0.f;
-        rv[H2 - 1] = fok[u] ? sd * fv[u] : 0.f;
-        rd[H2 - 1] = fok[u] ? sd * fd[u] : 0.f;
+        ra[H2 - 1] = fok[u] ? sa * ca(u) : 0.f;
+        rh[H2 - 1] = fok[u] ? sd * ch(u) : 0.f;
+        rv[H2 - 1] = fok[u] ? sd * cv(u) : 0.f;
+        rd[H2 - 1] = fok[u] ? sd * cd(u) : 0.f;
         fetch(u, min(q + PF, qend - 1));  // past the chunk: the chunk's last row again (see PK)
         float lo0 = 0.f, lo1 = 0.f, hi0 = 0.f, hi1 = 0.f;
   #pragma unroll

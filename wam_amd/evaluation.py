@@ -28,6 +28,16 @@ random_seed (42) and averages spearmanr's (rho, p-value) pair; its batch count i
 int(ceil(len) / batch_size) (sic). Tie order of equal importances: numpy's argsort is not
 stable and differs across numpy builds; the default ranks ties stably (``tie_order='stable'``,
 GPU), ``tie_order='numpy'`` ranks on the host with np.argsort like the reference.
+
+``mask_layout="mosaic"`` (an addition, opt-in; the default ``"pywt"`` is the path above) scores every
+coefficient by the WAM cell that displays it, for any wavelet and size the explainer can draw:
+pos[k] = the mosaic cell of coefficient k (frames.wam_cell_source), the ranking is that of the WAM's
+cells, n_comp = int(Hc * Wc / n_iter), and a coefficient no cell displays (the cropped border rows and
+columns of non-Haar bands, approximation cells a detail block overwrote) is held: every insertion and
+every deletion mask keeps it. Insertion's last and deletion's first image are therefore the exact
+reconstruction, the other end the reconstruction of the held coefficients alone. One
+wam_waverec2_ranked call serves a group of images (the float masks are never stored); mu-fidelity
+keeps wam_coeff_masks, its superpixel grid zoomed to the WAM canvas.
 Transform: the default (Resize((224, 224)) -- a no-op for 224 x 224 reconstructions --, ToTensor,
 Normalize(ImageNet)) runs fused on the GPU; a user ``transform`` (a callable on HWC uint8 numpy
 images) is applied on the host instead.
@@ -49,6 +59,7 @@ from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, chec
                        device_table, generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, rank_mask_rows,
                        resize_default, show_images, softmax, zoom_cell_map)
 from .evaluation3d import Eval3DWAM  # noqa: F401  (the volume evaluator, an addition: its own module)
+from .frames import wam_cell_source
 from .plan import get_plan
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d
@@ -70,8 +81,12 @@ class Eval2DWAM(WaveletAttribution2D):
 
     def __init__(self, model, wavelet="haar", J=3, device=None, mode="reflect", transform=None, approx_coeffs=False,
                  method="smooth", n_samples=25, batch_size=128, stdev_spread=0.25, random_seed=42, *,
-                 tie_order="stable", eval_batch=520, **wam_kw):
+                 tie_order="stable", eval_batch=520, mask_layout="pywt", **wam_kw):
         super().__init__(model, wavelet=wavelet, J=J, device=device, mode=mode, approx_coeffs=approx_coeffs)
+        if mask_layout not in ("pywt", "mosaic"):
+            raise ValueError("mask_layout must be 'pywt' or 'mosaic', got %r" % (mask_layout,))
+        self.mask_layout = mask_layout
+        self.ranked_route = -1  # 'mosaic': wam_waverec2_ranked's route, -1 = the plan's own (0 / 1 force one)
         self.smooted_grad_wam = WaveletAttribution2D(model, wavelet=wavelet, J=J, mode=mode,
                                                      approx_coeffs=approx_coeffs, n_samples=n_samples,
                                                      stdev_spread=stdev_spread, random_seed=random_seed,
@@ -91,22 +106,85 @@ class Eval2DWAM(WaveletAttribution2D):
     def _layout(self, plan):
         return array_layout(plan, self._dev)
 
+    def _mosaic_layout(self, plan):
+        """mask_layout='mosaic': (pos int32 [K] on the device, the WAM canvas (Hc, Wc), the number of
+        held coefficients) of the evaluation plan. pos[k] = the cell that displays coefficient k, or
+        Hc * Wc -- the extra slot of the ranking -- for a coefficient no cell displays."""
+        dev = self._dev
+        wam = self.smooted_grad_wam
+
+        def make():
+            xplan = get_plan(2, plan.shape, self.J, self.wavelet, wam.mode, dev)  # the explainer's
+            if list(xplan.band_shapes) != list(plan.band_shapes):
+                raise ValueError("mask_layout='mosaic': the explainer's bands %s are not the evaluation plan's %s"
+                                 % (xplan.band_shapes, plan.band_shapes))
+            src, shape = wam_cell_source(plan, wam.frame, wam.method)
+            cells = np.flatnonzero(src.reshape(-1) >= 0)
+            ks = src.reshape(-1)[cells]
+            assert np.unique(ks).size == ks.size and ks.max(initial=-1) < plan.coeff_numel, \
+                "a coefficient is displayed by two cells"
+            pos = np.full(plan.coeff_numel, shape[0] * shape[1], dtype=np.int32)
+            pos[ks] = cells
+            return torch.as_tensor(pos).to(dev), shape, int(plan.coeff_numel - ks.size)
+        return device_table(("mosaic2d", plan, wam.mode, wam.frame, wam.method, dev), make)
+
     def _altered_inputs(self, img, masks):
         """masks [M, AH, AW] float32 device -> model inputs [M, 3, 224, 224] (or uint8 HWC numpy
         images when a host transform is set)."""
         dev = self._dev
         C, H, W = img.shape
         plan = get_plan(2, (H, W), self.J, self.wavelet, "symmetric", dev)  # pywt.wavedec2's default mode
-        pos, shape = self._layout(plan)
+        if self.mask_layout == "mosaic":
+            pos, shape, _ = self._mosaic_layout(plan)
+        else:
+            pos, shape = self._layout(plan)
         if tuple(masks.shape[1:]) != tuple(shape):
             raise ValueError("operands could not be broadcast together with shapes (%d,%d) (%d,%d)"
                              % (shape + tuple(masks.shape[1:])))
         M = masks.shape[0]
+        mask_len = shape[0] * shape[1]
+        if self.mask_layout == "mosaic":  # the held slot: 1.0 in every mask
+            masks = torch.cat([masks.reshape(M, -1), torch.ones((M, 1), dtype=torch.float32, device=dev)], 1)
+            mask_len += 1
         coeffs = plan.wavedec(img.contiguous())
         masked = torch.empty(M * C * plan.coeff_numel, dtype=torch.float32, device=dev)
-        check(lib.wam_coeff_masks(plan.handle, C, ptr(coeffs), ptr(pos), M, shape[0] * shape[1],
+        check(lib.wam_coeff_masks(plan.handle, C, ptr(coeffs), ptr(pos), M, mask_len,
                                   ptr(masks.contiguous()), ptr(masked), stream_of(dev)))
         rec = plan.waverec(masked, M * C)[0]
+        return self._model_inputs(plan, rec, M, C)
+
+    def _ranked_inputs(self, imgs, wams, n_iter, deletion):
+        """mask_layout='mosaic': imgs [G, C, H, W] on the device, wams [G, Hc, Wc] (host) -> the model
+        inputs of all n_iter + 1 insertion (deletion) steps of every image, [G * (n_iter + 1), C, 224,
+        224], image-major."""
+        plan, rec = self._ranked_recs(imgs, wams, n_iter, deletion)
+        return self._model_inputs(plan, rec, rec.shape[0] * rec.shape[1], rec.shape[2])
+
+    def _ranked_recs(self, imgs, wams, n_iter, deletion):
+        """-> (the evaluation plan, the masked reconstructions [G, n_iter + 1, C, rec_h, rec_w]): one
+        wam_waverec2_ranked call, no mask stored."""
+        dev = self._dev
+        G, C, H, W = imgs.shape
+        plan = get_plan(2, (H, W), self.J, self.wavelet, "symmetric", dev)
+        pos, shape, _ = self._mosaic_layout(plan)
+        wams = np.asarray(wams)
+        if tuple(wams.shape[1:]) != tuple(shape):
+            raise ValueError("operands could not be broadcast together with shapes (%d,%d) (%d,%d)"
+                             % (shape + tuple(wams.shape[1:])))
+        cells = shape[0] * shape[1]
+        rank = descending_ranks(wams.reshape(G, cells), dev, self.tie_order)
+        # the held slot: below every threshold under insertion, above every one under deletion
+        held = torch.full((G, 1), np.iinfo(np.int32).max if deletion else -1, dtype=torch.int32, device=dev)
+        rank = torch.cat([rank, held], 1).contiguous()
+        coeffs = plan.wavedec(imgs.contiguous())
+        rec = plan.waverec2_ranked(coeffs, G, C, rank, pos, n_iter, int(cells / n_iter), deletion,
+                                   route=plan.ranked2_route() if self.ranked_route < 0 else self.ranked_route)
+        return plan, rec
+
+    def _model_inputs(self, plan, rec, M, C):
+        """reconstructions of M images of C planes -> model inputs (the default transform on the device,
+        a user transform on the host)."""
+        dev = self._dev
         rh, rw = plan.rec_shape
         if self.transform is not None:
             return self._host_transform(rec.view(M, C, rh, rw))
@@ -139,6 +217,13 @@ class Eval2DWAM(WaveletAttribution2D):
                                  stream_of(self._dev)))
         return masks
 
+    def _mask_hw(self, image_hw):
+        """The shape the superpixel grid is zoomed to: the image's own, or the WAM canvas ('mosaic')."""
+        if self.mask_layout != "mosaic":
+            return tuple(int(v) for v in image_hw)
+        plan = get_plan(2, tuple(int(v) for v in image_hw), self.J, self.wavelet, "symmetric", self._dev)
+        return self._mosaic_layout(plan)[1]
+
     def _upsample(self, grid_masks, grid_size, hw):
         cell = cell_map(grid_size, hw, self._dev)
         g = torch.as_tensor(np.ascontiguousarray(grid_masks), dtype=torch.float32).to(self._dev)
@@ -167,11 +252,17 @@ class Eval2DWAM(WaveletAttribution2D):
         scores, predicted_probs = [], []
         per_call = max(1, self.eval_batch // (n_iter + 1))
         for s0 in range(0, n_samples, per_call):
-            batch = [self._altered_inputs(images[s], self._rank_masks(self.grad_wams[s], n_iter, mode == "deletion"))
-                     for s in range(s0, min(n_samples, s0 + per_call))]
+            group = range(s0, min(n_samples, s0 + per_call))
+            if self.mask_layout == "mosaic":
+                inputs = self._ranked_inputs(torch.stack([images[s] for s in group]),
+                                             np.stack([self.grad_wams[s] for s in group]), n_iter, mode == "deletion")
+            else:
+                inputs = torch.cat([self._altered_inputs(images[s], self._rank_masks(self.grad_wams[s], n_iter,
+                                                                                    mode == "deletion"))
+                                    for s in group])
             with torch.no_grad():
-                preds = self.model(torch.cat(batch)).float().cpu().numpy()
-            for p in class_curves(preds, n_iter + 1, [y[s] for s in range(s0, s0 + len(batch))]):
+                preds = self.model(inputs).float().cpu().numpy()
+            for p in class_curves(preds, n_iter + 1, [y[s] for s in group]):
                 scores.append(compute_auc(p))
                 predicted_probs.append(p)
         return scores, predicted_probs
@@ -196,7 +287,7 @@ class Eval2DWAM(WaveletAttribution2D):
             base = softmax(self.model(xd).float().cpu().numpy())
         base_probs = [base[i, y[i]] for i in range(len(y))]
         images = self._images(x)
-        H, W = xd.shape[2], xd.shape[3]
+        H, W = self._mask_hw(xd.shape[2:])
         w, r = gaussian_weights(2)
         dev = self._dev
         mu = []
@@ -226,7 +317,7 @@ class Eval2DWAM(WaveletAttribution2D):
         """src/evaluators.py:769-801: the uniform random superpixel mask whose reconstruction
         has the lowest class probability."""
         source_masks = np.random.uniform(size=(sample_size, grid_size, grid_size))
-        up, _ = self._upsample(source_masks, grid_size, tuple(image.shape[1:]))
+        up, _ = self._upsample(source_masks, grid_size, self._mask_hw(image.shape[1:]))
         ys = self._evaluate_batched(self._altered_inputs(image, up), label, batch_size)
         return source_masks[int(np.argmin(ys)), :, :]
 

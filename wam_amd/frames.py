@@ -112,6 +112,35 @@ def ig_frames(plan, n, frame, device):
     return v
 
 
+def wam_cell_source(plan, frame, method, n=1):
+    """The cell-to-coefficient map of the WAM the explainer returns for `plan`: (src, (Hc, Wc)), src the
+    host int64 canvas [Hc, Wc] holding the per-plane coefficient offset behind every cell, or -1 where a
+    cell shows none. method 'smooth': the canvas of smooth_frame; 'integratedgrad': the gradient map of
+    ig_frames (cropped to 224 x 224 under 'legacy'). The legacy shape errors are those of the two
+    functions (n words their message). A coefficient appears in at most one cell; those in none are
+    the cropped border rows / columns of non-Haar bands and approximation cells a detail block overwrote."""
+    H, W = plan.shape
+    if frame not in ("legacy", "native"):
+        raise ValueError("frame must be 'legacy' or 'native'")
+    if method not in ("smooth", "integratedgrad"):
+        raise ValueError("method must be 'smooth' or 'integratedgrad'")
+    if frame == "native":
+        src, _ = _mosaic_2d(plan, (H, W), (H, W))
+    else:
+        r = 2 * plan.band_shapes[-1][1]
+        src, _ = _mosaic_2d(plan, (r, r), (224, 224))
+        if method == "smooth":
+            if (r, r) != (H, W):
+                raise _bcast_error((n, H, W), (n, r, r))
+        else:
+            src = src[:224, :224]
+            if src.shape != (H, W):
+                raise ValueError("could not broadcast input array from shape %s into shape %s" % (
+                    str((n,) + src.shape).replace(" ", ""), str((n, H, W)).replace(" ", "")))
+    src = np.ascontiguousarray(src)
+    return src, tuple(src.shape)
+
+
 def mosaic_map(plan, canvas_hw, base_hw, device):
     """Generic access (used by BaseWAM2D.__call__ and tests)."""
     key = ("mosaic", plan, tuple(canvas_hw), tuple(base_hw))

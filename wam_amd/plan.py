@@ -145,6 +145,42 @@ class Plan:
                                      int(bool(deletion)), route, ptr(out), ptr(ws), stream_of(flat.device)))
         return out
 
+    def ranked2_route(self):
+        """The route waverec2_ranked takes by itself (wam_waverec2_ranked_route): 0 = mask expansion +
+        waverec, 1 = the fused plane-resident kernel. 2D plans only."""
+        r = lib.wam_waverec2_ranked_route(self._h)
+        if r < 0:
+            check(-r)
+        return r
+
+    def waverec2_ranked(self, flat, images, channels, rank, pos, n_iter, n_comp, deletion, route=-1, out=None):
+        """The n_iter + 1 masked reconstructions of each of `images` images of `channels` planes
+        (wam_waverec2_ranked): flat band-major coefficients of the images * channels planes, rank int32
+        [images, rank_len] and pos int32 [coeff_numel] -> [images, n_iter + 1, channels, *rec_shape].
+        route: -1 the plan's own, 0 expansion + waverec, 1 the fused kernel; the workspace of either comes
+        from the plan."""
+        require_cuda(flat, "coefficients")
+        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
+        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise TypeError("wam_amd: rank and pos must be int32")
+        if (flat.numel() != images * channels * self.coeff_numel or pos.numel() != self.coeff_numel
+                or rank.dim() != 2 or rank.shape[0] != images):
+            raise ValueError("expected %d x %d x %d coefficients, %d positions and %d rank rows"
+                             % (images, channels, self.coeff_numel, self.coeff_numel, images))
+        M = int(n_iter) + 1
+        if out is None:
+            out = torch.empty((images, M, channels) + self.rec_shape, dtype=torch.float32, device=flat.device)
+        ws = None
+        n = int(lib.wam_waverec2_ranked_workspace_bytes(self._h, images, channels, n_iter, route))
+        if n:
+            ws = self._ws.get("ranked2")
+            if ws is None or ws.numel() < n:
+                ws = self._ws["ranked2"] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib.wam_waverec2_ranked(self._h, images, channels, ptr(flat), ptr(rank), rank.shape[1], ptr(pos),
+                                      n_iter, n_comp, int(bool(deletion)), route, ptr(out), ptr(ws),
+                                      stream_of(flat.device)))
+        return out
+
     def waverec_bf16_nhwc(self, flat, batch, channels, alphas=None, out=None):
         """flat band-major coefficients of `batch` planes (images x channels) -> the reconstruction as
         bf16 images [n_alpha * batch / channels, channels, *rec_shape] in channels_last memory (the

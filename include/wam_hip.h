@@ -485,6 +485,62 @@ int    wam_waverec2_ranked(const wam_plan* plan, int64_t images, int channels, c
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Insertion / deletion of audio WAMs with every coefficient ranked by its own gradient
+ * (Eval1DWAM with mask_layout="coeffs"): the n_iter + 1 masked reconstructions of every clip and their
+ * peak values in one call, then the division. These are the entries of 1D plans. The selection rule,
+ * the layout of coeffs, rank and pos and the pad rule are exactly those of wam_rank_mask_coeffs:
+ * thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len; mask m of set s keeps the
+ * coefficient at per-item offset k when (rank[s, pos[k]] < thr(m)) != (deletion != 0), a pos[k] of -1 or
+ * outside [0, rank_len) reading as rank -1 (kept by every mask under insertion, dropped by every mask
+ * under deletion); two coefficients may share a slot; a kept value is multiplied by 1.0f and a dropped
+ * one by 0.0f, the approximation like any other band. out [sets * (n_iter + 1), rec_len] float32,
+ * rec_len = wam_plan_rec_shape: row s * (n_iter + 1) + m = wam_waverec of set s masked by m.
+ * row_max [sets * (n_iter + 1)] float32 (device, may be NULL): row_max[r] = the signed maximum of out row
+ * r over rec_len, bit-equal to the maximum wam_peak_normalize reduces, a zero maximum written as
+ * +0.0f; inputs are finite, as in wam_peak_normalize's contract. Two routes compute both, bit-identical
+ * to each other in out and in row_max:
+ *   route 0: the masked sets are written band-major into the workspace (wam_rank_mask_coeffs), the
+ *     plan's wam_waverec reads them, and a max-only reduction pass fills row_max when it is given: every
+ *     1D plan, any alignment of coeffs, rank, pos and out;
+ *   route 1: plans whose wam_waverec runs the persistent fused tile kernel on every tile (filters up to
+ *     20 taps, levels <= 8, the register and LDS footprint of that kernel, a non-periodic mode, not
+ *     WAM_PLAN_GENERIC; an (L, levels) whose ranked kernel would spill registers is excluded too --
+ *     none is today): a pre-pass writes the ranking in coefficient order once per set (sets * K int32 of
+ *     workspace), and the synthesis applies the threshold as it stages its coefficients; no masked
+ *     coefficient is stored and each workgroup adds the maximum of the outputs it wrote to row_max with
+ *     one atomic (row_max is set to -inf first; the maximum does not depend on the order). Any alignment.
+ * ---------------------------------------------------------------------------------------------- */
+/* the route a plan takes by itself: 0 = expansion + wam_waverec (+ maxima), 1 = the fused tile kernel
+ * wherever it applies (its slowest round beat route 0's fastest at every filter length from 2 to 20 taps,
+ * profiles/eval1d_ranked_kbench.txt). Works on host-only plans; negative for a NULL or non-1D plan. */
+int    wam_waverec1_ranked_route(const wam_plan* plan);
+/* bytes of workspace wam_waverec1_ranked needs on `route`: route 1 the rank table, sets * K int32 rounded
+ * up to 16 bytes; route 0 sets * (n_iter + 1) * K floats, rounded up to 16 bytes, followed by
+ * wam_plan_workspace_bytes(plan, sets * (n_iter + 1)); -1 (the plan's own) route 0's size, which is the
+ * fallback's and holds route 1's table too. 0 for invalid arguments. */
+size_t wam_waverec1_ranked_workspace_bytes(const wam_plan* plan, int64_t sets, int64_t n_iter, int route);
+/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
+ * wam_waverec1_ranked_workspace_bytes(plan, sets, n_iter, route) bytes. Forcing route 1 on a plan it does
+ * not serve returns WAM_ERR_UNSUPPORTED and launches nothing; with route -1 a call that route 1 cannot
+ * take runs route 0. A non-1D plan: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG as for wam_waverec_ranked (a
+ * NULL plan, coeffs, rank, pos or out, sets < 0, rank_len < 1 or > INT32_MAX, n_iter < 1, n_comp < 0, a
+ * host-only plan, another route value, more than 65535 * 16 masks), for more than INT32_MAX output rows
+ * and for a NULL or misaligned workspace; nothing is launched then. sets == 0 returns WAM_OK. */
+int    wam_waverec1_ranked(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
+                           int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
+                           int route /* -1: the plan's own */, float* out /* [sets*(n_iter+1), rec_len] */,
+                           float* row_max /* [sets*(n_iter+1)] or NULL */, void* workspace, void* stream);
+/* The second half of wam_peak_normalize, given the maxima (wam_waverec1_ranked's row_max): out[r, i] =
+ * in[r, i] / row_max[r] in IEEE fp32 division (correctly rounded, no reciprocal multiply); silent[r]
+ * (int32, device, may be NULL) = (row_max[r] == 0). A silent row divides by zero as IEEE does; with
+ * zero_silent != 0 it is copied unchanged instead. out may be `in` (in place). Each row is read once and
+ * written once, with 16-byte accesses when len is a multiple of 4 and in and out are 16-byte aligned.
+ * WAM_ERR_INVALID_ARG: rows < 0 or > INT32_MAX, len < 1, a NULL in, row_max or out, more than INT32_MAX
+ * spans of 4096 elements over all rows. rows == 0 returns WAM_OK. */
+int    wam_peak_divide(int64_t rows, int64_t len, const float* in, const float* row_max, float* out,
+                       int32_t* silent, int zero_silent, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * WAMAnalyzer2D (src/analyzers.py:16-203, src/analyzers_helpers.py:6-134): necessary components
  * (quantile thresholds on the WAM map) and scale isolation (one mask per level). The reference's
  * per-image, per-quantile CPU loop (3 x pywt.wavedec2 -> coeffs_to_array -> arr * (grad_wam >= t) ->

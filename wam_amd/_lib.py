@@ -107,6 +107,11 @@ _SIGS = {
     "wam_waverec2_ranked_workspace_bytes": (ctypes.c_size_t, [c_vp, c_i64, c_int, c_i64, c_int]),
     "wam_waverec2_ranked": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp,
                                     c_vp, c_vp]),
+    "wam_waverec1_ranked_route": (c_int, [c_vp]),
+    "wam_waverec1_ranked_workspace_bytes": (ctypes.c_size_t, [c_vp, c_i64, c_i64, c_int]),
+    "wam_waverec1_ranked": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp,
+                                    c_vp, c_vp]),
+    "wam_peak_divide": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "wam_threshold_mask_coeffs": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_int,
                                           ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_vp]),
     "wam_quantize_normalize_ex": (c_int, [c_i64, c_int, c_i64, c_vp, c_int, ctypes.POINTER(c_f32),

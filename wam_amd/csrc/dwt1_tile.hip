@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "quantize.hpp"
 #include "rng.hpp"
 
 namespace {
@@ -704,6 +705,60 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
+// k_dwt1_syn_ranked's level loop: the J levels of one staged unit, coarse to fine, FMA for FMA the loop
+// in k_dwt1_syn_int below (same tap order, same packed chains), plus the signed maximum mx of the
+// outputs this thread stored. Kept beside that loop rather than shared with it: calling this from
+// k_dwt1_syn_int changed the register allocation of 11 of its 80 instantiations.
+template <int L, int J>
+__device__ __forceinline__ void syn_int_levels(const float* stage, float* abuf0, float* abuf1, const float (&rlo)[L],
+                                               const float (&rhi)[L], const Dwt1Geom& g, int u0, int nout0,
+                                               float* __restrict__ o, int tid, float& mx) {
+  using Sh = SynShape<L, J>;
+  constexpr int H2 = L / 2;
+  const bool pairs_aligned = (reinterpret_cast<uintptr_t>(o) & 7) == 0;
+  static_for<0, J>([&](auto iv) __attribute__((always_inline)) {
+    constexpr int ll = J - 1 - decltype(iv)::value;  // coarse to fine
+    // coefficient i of level ll sits at i - (u0 >> (ll + 1)); the pair q = outputs (2q, 2q + 1)
+    // relative to the level's first output u0 >> ll reads coefficients q .. q + H2 - 1
+    constexpr int CA = Sh::cum(J), CD = Sh::cum(ll);  // constants here: no run-time call of the recursion
+    const float* ain = ll == J - 1 ? stage + CA : ((ll & 1) ? abuf0 : abuf1);
+    const float* din = stage + CD;
+    float* aout = (ll & 1) ? abuf1 : abuf0;
+    constexpr int NOUT = ll ? syn_n<L>(ll > 0 ? ll - 1 : 0) : 2 * kTile0;
+    // outputs past the approximation's band (or the signal) are zeros / not written
+    const int vout = ll ? g.m[ll > 0 ? ll - 1 : 0] - (u0 >> ll) : nout0 - u0;
+    for (int q = tid; q < (NOUT + 1) / 2; q += kT1) {
+      // (ya, yb) as one packed chain: tap pairs (2j, 2j + 1) times the broadcast coefficient,
+      // each output keeping the scalar chain's tap order (same sums)
+      f2v y = {0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < H2; ++j) {
+        const float av = ain[q + H2 - 1 - j], dv = din[q + H2 - 1 - j];
+        y = __builtin_elementwise_fma(f2v{rlo[2 * j], rlo[2 * j + 1]}, (f2v)av, y);
+        y = __builtin_elementwise_fma(f2v{rhi[2 * j], rhi[2 * j + 1]}, (f2v)dv, y);
+      }
+      const float ya = y.x, yb = y.y;
+      if (ll) {
+        aout[2 * q] = 2 * q < vout ? ya : 0.f;
+        if (NOUT % 2 == 0 || 2 * q + 1 < NOUT) aout[2 * q + 1] = 2 * q + 1 < vout ? yb : 0.f;
+      } else if (pairs_aligned && 2 * q + 1 < vout) {
+        *reinterpret_cast<float2*>(o + 2 * q) = make_float2(ya, yb);
+        mx = fmaxf(mx, fmaxf(ya, yb));
+      } else {
+        if (2 * q < vout) {
+          o[2 * q] = ya;
+          mx = fmaxf(mx, ya);
+        }
+        if (2 * q + 1 < vout) {
+          o[2 * q + 1] = yb;
+          mx = fmaxf(mx, yb);
+        }
+      }
+    }
+    __syncthreads();
+  });
+}
+
 template <int L, int J>
 __global__ void __launch_bounds__(kT1) k_dwt1_syn_int(const float* __restrict__ coeffs, float* __restrict__ out,
                                                      const float* __restrict__ filt, Dwt1Geom g, int nout0, float sc,
@@ -795,6 +850,119 @@ __global__ void __launch_bounds__(kT1) k_dwt1_syn_int(const float* __restrict__ 
       }
       __syncthreads();
     });
+  }
+}
+
+// Ranked synthesis (wam_waverec1_ranked, route 1): k_dwt1_syn_int at scale 1.0f with the rank threshold
+// of the mask expansion applied as a unit's coefficient footprint is staged (pf * keep, keep = 1.0f or
+// 0.0f), so the M = n_iter + 1 masked coefficient sets of a signal are never written. A unit is (set,
+// tile, chunk of masks), chunk fastest over XCD-swizzled workgroups: its coefficients and their ranks
+// (rtab, coefficient order) are fetched once into registers, one unit ahead, and every mask of the
+// chunk is staged from them; the chunks of one (set, tile) run on one XCD and share its L2. After the
+// staging the level loop is a copy of k_dwt1_syn_int's (syn_int_levels), so every output has route 0's bits.
+// row_max (may be NULL, -inf on entry): the signed maximum of each output row, one atomic per (row, tile).
+struct Ranked1Args {
+  const int32_t* rtab;  // [sets, K] int32: the rank of coefficient k's mask slot, -1 for the pad column
+  int64_t K;
+  int rank_len, n_iter, deletion, mchunk, nchunks, tiles;
+  int64_t n_comp;
+  float* row_max;
+};
+
+// max over concurrent writers of a float that starts at -inf: the integer order of IEEE bits
+// (signed max for v >= 0, unsigned min for v < 0); v + 0.0f turns -0.0f into +0.0f
+__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
+  v += 0.f;
+  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+  else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
+}
+
+template <int L, int J>
+__global__ void __launch_bounds__(kT1) k_dwt1_syn_ranked(const float* __restrict__ coeffs, float* __restrict__ out,
+                                                        const float* __restrict__ filt, Dwt1Geom g, int nout0,
+                                                        int64_t units, Ranked1Args ra) {
+  using Sh = SynShape<L, J>;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float red[kT1 / 64];
+  const int tid = threadIdx.x;
+  float rlo[L], rhi[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    rlo[k] = filt[k];
+    rhi[k] = filt[L + k];
+  }
+  float* stage = smem;
+  float* abuf0 = smem + Sh::stage;
+  float* abuf1 = abuf0 + Sh::abuf;
+  float pf[Sh::nslots];
+  int32_t rk[Sh::nslots];
+  // unit -> (set, tile's first output, chunk)
+  auto unit_geom = [&](int64_t u, int64_t& item, int& u0, int& chunk) {
+    const int64_t st = u / ra.nchunks;
+    chunk = (int)(u - st * ra.nchunks);
+    item = st / ra.tiles;
+    u0 = (int)(st - item * ra.tiles) * (2 * kTile0);
+  };
+  auto prefetch = [&](int64_t u) __attribute__((always_inline)) {
+    int64_t item;
+    int u0, chunk;
+    unit_geom(u < units ? u : units - 1, item, u0, chunk);
+    static_for<0, J + 1>([&](auto sv) __attribute__((always_inline)) {
+      constexpr int s = decltype(sv)::value;
+      constexpr int l = s < J ? s : J - 1;
+      constexpr int LEN = Sh::len(s), NS = Sh::slots(s), S0 = Sh::slot0(s);
+      const int64_t boff = s < J ? g.off_d[l] : g.off_a;
+      const float* src = coeffs + g.items * boff + item * (int64_t)g.m[l] + (u0 >> (l + 1));
+      const int32_t* rsrc = ra.rtab + item * ra.K + boff + (u0 >> (l + 1));
+      // the last tile's ranges run past the band: coefficient and rank loads clamped alike
+      // (unconditional), zeros put in when the unit is staged (k_dwt1_syn_int's rule)
+      const int vlen = min(LEN, g.m[l] - (u0 >> (l + 1)));
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const int i = tid + k * kT1;
+        const int ic = i < vlen ? i : vlen - 1;
+        pf[S0 + k] = src[ic];
+        rk[S0 + k] = rsrc[ic];
+      }
+    });
+  };
+  const int M = ra.n_iter + 1;
+  int64_t u = wam_xcd_block(blockIdx.x, gridDim.x);
+  if (u < units) prefetch(u);
+  for (; u < units; u += gridDim.x) {
+    int64_t item;
+    int u0, chunk;
+    unit_geom(u, item, u0, chunk);
+    const int m0 = chunk * ra.mchunk, m1 = min(M, m0 + ra.mchunk);
+    for (int m = m0; m < m1; ++m) {
+      // thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len (maskexpand.hpp mask_thr)
+      int64_t t64 = (int64_t)m * ra.n_comp;
+      if (m >= ra.n_iter || t64 > ra.rank_len) t64 = ra.rank_len;
+      const int thr = m == 0 ? 0 : (int)t64;
+      const bool del = ra.deletion != 0;
+      static_for<0, J + 1>([&](auto sv) __attribute__((always_inline)) {
+        constexpr int s = decltype(sv)::value;
+        constexpr int l = s < J ? s : J - 1;
+        constexpr int LEN = Sh::len(s), NS = Sh::slots(s), S0 = Sh::slot0(s), C = Sh::cum(s);
+        const int vlen = min(LEN, g.m[l] - (u0 >> (l + 1)));
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+          const int i = tid + k * kT1;
+          const float keep = ((rk[S0 + k] < thr) != del) ? 1.f : 0.f;
+          if (i < LEN) stage[C + i] = i < vlen ? pf[S0 + k] * keep : 0.f;
+        }
+      });
+      __syncthreads();
+      if (m + 1 == m1) prefetch(u + gridDim.x);  // in flight while the chunk's last levels run
+      const int64_t row = item * M + m;
+      float mx = -INFINITY;
+      syn_int_levels<L, J>(stage, abuf0, abuf1, rlo, rhi, g, u0, nout0, out + row * (int64_t)nout0 + u0, tid,
+                                 mx);
+      if (ra.row_max) {  // uniform
+        mx = block_reduce(mx, MaxOp(), red);
+        if (tid == 0) atomic_max_f32(ra.row_max + row, mx);
+      }
+    }
   }
 }
 
@@ -1116,5 +1284,61 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
     }
     WAM_LAUNCH_CHECK();
   }
+  return WAM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The fused route of wam_waverec1_ranked (evaluate1d.hip): plans whose wam_waverec runs
+// k_dwt1_syn_int on every tile. The ranked kernel keeps a rank beside every prefetched coefficient
+// (2 * nslots registers); every (L, J) k_dwt1_syn_int takes compiles without scratch.
+bool dwt1_syn_ranked_supported(const wam_plan* p) {
+  return p->ndim == 1 && p->routes.syn == WAM_WHOLE_TILE1 && p->levels <= 8 && syn_int_fits(p->L, p->levels);
+}
+
+int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rtab,
+                                      int64_t rank_len, int64_t n_iter, int64_t n_comp, int deletion, float* out,
+                                      float* row_max, hipStream_t st) {
+  if (!dwt1_syn_ranked_supported(p) || !rtab) return WAM_ERR_UNSUPPORTED;
+  const int nout = (int)p->rec_shape[0];
+  const int64_t M = n_iter + 1, K = p->band_off[p->nbands];
+  if (M > 65535 * 16 || rank_len > INT32_MAX) return WAM_ERR_INVALID_ARG;
+  Dwt1Geom g = make_geom1(p, (int)p->lin[0][0], p->mode, sets);
+  g.tiles = (nout + 2 * kTile0 - 1) / (2 * kTile0);
+  int dev = 0, cus = 256;
+  WAM_HIP_CHECK(hipGetDevice(&dev));
+  WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  // masks per unit: up to 16 (the mask expansion's chunk), fewer while the (set, tile, chunk) units
+  // would not fill the persistent grid twice
+  const int64_t st_units = sets * g.tiles;
+  int64_t mchunk = std::min<int64_t>(16, M);
+  while (mchunk > 1 && st_units * ((M + mchunk - 1) / mchunk) < 4LL * cus) mchunk = (mchunk + 1) / 2;
+  const int64_t nchunks = (M + mchunk - 1) / mchunk;
+  const int64_t units = st_units * nchunks;
+  if (units > 0x7fffffff) return WAM_ERR_UNSUPPORTED;
+  const Ranked1Args ra{rtab, K, (int)rank_len, (int)n_iter, deletion, (int)mchunk, (int)nchunks, g.tiles, n_comp, row_max};
+  const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;
+  // algorithmic bytes: coefficients and ranks once per chunk, every reconstruction once
+  WamTimer tm(st, "k_dwt1_syn_ranked", 4.0 * (2.0 * (double)sets * K * nchunks + (double)sets * M * nout));
+  int rc = WAM_ERR_UNSUPPORTED;
+#define WAM_D1SR(LL, JJ)                                                                                          \
+  if (p->L == LL && g.J == JJ) {                                                                                  \
+    using Sh = SynShape<LL, JJ>;                                                                                  \
+    if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_ranked<LL, JJ>, kLds1Cap)) return e;                       \
+    int wgs = 2;                                                                                                  \
+    WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_dwt1_syn_ranked<LL, JJ>, kT1,              \
+                                                               Sh::lds_bytes));                                   \
+    const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);                               \
+    hipLaunchKernelGGL((k_dwt1_syn_ranked<LL, JJ>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs,   \
+                       out, filt, g, nout, units, ra);                                                            \
+    rc = WAM_OK;                                                                                                  \
+  }
+#define WAM_D1SRJ(LL) WAM_D1SR(LL, 1) WAM_D1SR(LL, 2) WAM_D1SR(LL, 3) WAM_D1SR(LL, 4) WAM_D1SR(LL, 5) \
+                      WAM_D1SR(LL, 6) WAM_D1SR(LL, 7) WAM_D1SR(LL, 8)
+  WAM_D1SRJ(2) WAM_D1SRJ(4) WAM_D1SRJ(6) WAM_D1SRJ(8) WAM_D1SRJ(10) WAM_D1SRJ(12) WAM_D1SRJ(14) WAM_D1SRJ(16)
+  WAM_D1SRJ(18) WAM_D1SRJ(20)
+#undef WAM_D1SRJ
+#undef WAM_D1SR
+  if (rc) return rc;
+  WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

@@ -196,6 +196,14 @@ int launch_rank_mask_coeffs3(const wam_plan* p, int64_t sets, const float* coeff
                              int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
                              float* out, hipStream_t st);
 
+// wam_waverec1_ranked (evaluate1d.hip), route 1: k_dwt1_syn_int with the rank threshold applied as a
+// unit's coefficients are staged (dwt1_tile.hip). rtab [sets, K] int32: the ranks in coefficient order
+// (evaluate1d.hip writes it). out [sets * (n_iter + 1), rec_len]; row_max (may be NULL) must hold -inf.
+bool dwt1_syn_ranked_supported(const wam_plan* p);
+int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rtab,
+                                      int64_t rank_len, int64_t n_iter, int64_t n_comp, int deletion, float* out,
+                                      float* row_max, hipStream_t st);
+
 // wam_waverec2_ranked (evaluate2d.hip), route 1: k_plane_syn with the rank threshold applied as the
 // coefficient rows are loaded (dwt2_plane.hip). rtab: dwt2_plane_ranked_table_bytes of workspace, the
 // ranks in coefficient order. out [images, n_iter + 1, channels, rec_h, rec_w].

@@ -60,7 +60,7 @@ from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, chec
                        resize_default, show_images, softmax, zoom_cell_map)
 from .evaluation3d import Eval3DWAM  # noqa: F401  (the volume evaluator, an addition: its own module)
 from .frames import wam_cell_source
-from .plan import get_plan
+from .plan import get_plan, peak_divide
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d
 from .wam_2D import WaveletAttribution2D
@@ -348,6 +348,25 @@ def coeff_slot_map(length, levels, band_lens, n_masks=1):
     return np.concatenate(parts).astype(np.int32)
 
 
+def coeff_identity_map(band_lens, grad_band_lens):
+    """mask_layout='coeffs': the mask slot of every coefficient of the evaluation plan whose bands (A_J,
+    D_J, ..., D_1) are band_lens long -- its own band-major per-item offset, pos[k] = k, so rank_len = K,
+    no pad column and no held slot. grad_band_lens: the band lengths of the explainer's gradients, which
+    must be the plan's. Returns int32 [sum(n_i)]."""
+    if [int(n) for n in grad_band_lens] != [int(n) for n in band_lens]:
+        raise ValueError("mask_layout='coeffs': the explainer's bands %s are not the evaluation plan's %s"
+                         % ([int(n) for n in grad_band_lens], [int(n) for n in band_lens]))
+    return np.arange(int(sum(band_lens)), dtype=np.int32)
+
+
+def rank_thresholds(n_iter, rank_len):
+    """(n_comp, [thr(0), ..., thr(n_iter)]) of a ranking with rank_len slots, as the rank-mask kernels
+    apply them: n_comp = int(rank_len / n_iter), thr(0) = 0, thr(m) = min(m * n_comp, rank_len),
+    thr(n_iter) = rank_len (insertion keeps the ranks below thr(m), deletion the others)."""
+    n_comp = int(rank_len / n_iter)
+    return n_comp, [0] + [min(m * n_comp, rank_len) for m in range(1, n_iter)] + [rank_len]
+
+
 class Eval1DWAM(WaveletAttribution1D):
     """src/evaluators.py:39-306 -- insertion / deletion on the wavelet coefficients or on the mel
     spectrogram, faithfulness of spectra (Parekh et al.) and input fidelity (Paissan et al.) of an
@@ -372,13 +391,28 @@ class Eval1DWAM(WaveletAttribution1D):
     wavelet-target insertion / deletion score is NaN (``silent='nan'``, the default); k_mel_fwd's
     clamp would swallow a NaN waveform, so the rows wam_peak_normalize flags get NaN logits after
     the forward. ``silent='zero'`` leaves such a row silent and the scores finite. Ties: numpy's
-    argsort is not stable; ``tie_order`` as in Eval2DWAM."""
+    argsort is not stable; ``tie_order`` as in Eval2DWAM.
+
+    ``mask_layout="coeffs"`` (an addition, opt-in; the default ``"reference"`` is the path above, bit for
+    bit and call for call) scores every wavelet's maps on the wavelet target: each coefficient of the
+    evaluation plan is ranked by its own gradient (the slot map is the identity on the band-major
+    offset, rank_len = K = coeff_numel, no pad column; the explainer's band lengths must be the plan's,
+    a ValueError otherwise), thr(m) = min(m * int(K / n_iter), K) with the last mask full. Per group of
+    clips: one wam_wavedec, one wam_waverec1_ranked (all n_iter + 1 reconstructions and their signed
+    maxima; ``ranked_route`` = -1 takes the plan's own route, 0 / 1 force one), one wam_peak_divide in
+    place with the silent flags, then the same mel front-end and model. The silent end (insertion's
+    first row, deletion's last) is handled by ``silent`` as above; the mel target has no layout."""
 
     def __init__(self, model, batch_size=128, wavelet="haar", J=3, method="smooth", mode="reflect", device=None,
                  approx_coeffs=False, n_mels=128, n_fft=1024, sample_rate=44100, n_samples=25, stdev_spread=0.001,
-                 random_seed=42, *, tie_order="stable", eval_batch=520, silent="nan", **wam_kw):
+                 random_seed=42, *, tie_order="stable", eval_batch=520, silent="nan", mask_layout="reference",
+                 **wam_kw):
+        if mask_layout not in ("reference", "coeffs"):
+            raise ValueError("mask_layout must be 'reference' or 'coeffs', got %r" % (mask_layout,))
         super().__init__(model, wavelet, J, method, mode, device, approx_coeffs, n_mels, n_fft, sample_rate, n_samples,
                          stdev_spread, random_seed)
+        self.mask_layout = mask_layout
+        self.ranked_route = -1  # 'coeffs': wam_waverec1_ranked's route, -1 = the plan's own (0 / 1 force one)
         self.grad_wams = None
         self.batch_size = batch_size
         self.gradwam = WaveletAttribution1D(model, wavelet=wavelet, J=J, method=method, mode=mode, device=device,
@@ -415,6 +449,8 @@ class Eval1DWAM(WaveletAttribution1D):
         wave = (wave[None] if wave.dim() == 1 else wave[samples]).contiguous()
         sets, M = len(samples), n_iter + 1
         plan = get_plan(1, (wave.shape[-1],), self.J, self.wavelet, "reflect", dev)  # ptwt.wavedec's default mode
+        if self.mask_layout == "coeffs":
+            return self._auc_from_coeffs(plan, gradients, wave, samples, mode, n_iter)
         pos = self._slot_map(plan, M)
         K = plan.coeff_numel
         g = np.stack([np.concatenate([np.asarray(b)[s] for b in gradients]) for s in samples])
@@ -429,6 +465,22 @@ class Eval1DWAM(WaveletAttribution1D):
         flags = torch.empty(sets * M, dtype=torch.int32, device=dev)
         check(lib.wam_peak_normalize(sets * M, rec.shape[1], ptr(rec), ptr(rec), ptr(flags),
                                      int(self.silent == "zero"), stream_of(dev)))
+        self._silent_rows = flags.bool()
+        return self._mel(rec)
+
+    def _auc_from_coeffs(self, plan, gradients, wave, samples, mode, n_iter):
+        """auc_from_wavelet under mask_layout='coeffs': wave [sets, W] on the device."""
+        dev = self._dev
+        sets, M, K = len(samples), n_iter + 1, plan.coeff_numel
+        band_lens = [s[0] for s in plan.band_shapes]
+        pos_host = coeff_identity_map(band_lens, [np.asarray(b).shape[1] for b in gradients])
+        pos = device_table(("coeffs1d", plan, dev), lambda: torch.as_tensor(pos_host).to(dev))
+        g = np.stack([np.concatenate([np.asarray(b)[s] for b in gradients]) for s in samples])
+        rank = descending_ranks(np.abs(g), dev, self.tie_order)
+        coeffs = plan.wavedec(wave)
+        rec, row_max = plan.waverec1_ranked(coeffs, sets, rank, pos, n_iter, rank_thresholds(n_iter, K)[0],
+                                            mode == "deletion", route=self.ranked_route)
+        rec, flags = peak_divide(rec.view(sets * M, -1), row_max, zero_silent=self.silent == "zero")
         self._silent_rows = flags.bool()
         return self._mel(rec)
 

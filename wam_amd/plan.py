@@ -181,6 +181,43 @@ class Plan:
                                       stream_of(flat.device)))
         return out
 
+    def ranked1_route(self):
+        """The route waverec1_ranked takes by itself (wam_waverec1_ranked_route): 0 = mask expansion +
+        waverec, 1 = the fused tile kernel. 1D plans only."""
+        r = lib.wam_waverec1_ranked_route(self._h)
+        if r < 0:
+            check(-r)
+        return r
+
+    def waverec1_ranked(self, flat, sets, rank, pos, n_iter, n_comp, deletion, route=-1, out=None, want_max=True):
+        """The n_iter + 1 masked reconstructions of each of `sets` signals and their signed maxima
+        (wam_waverec1_ranked): flat band-major coefficients of the sets, rank int32 [sets, rank_len] and
+        pos int32 [coeff_numel] as for wam_rank_mask_coeffs -> (out [sets * (n_iter + 1), rec_len],
+        row_max [sets * (n_iter + 1)] or None without want_max). route: -1 the plan's own, 0 expansion +
+        waverec, 1 the fused kernel; the workspace of either comes from the plan."""
+        require_cuda(flat, "coefficients")
+        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
+        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise TypeError("wam_amd: rank and pos must be int32")
+        if (flat.numel() != sets * self.coeff_numel or pos.numel() != self.coeff_numel or rank.dim() != 2
+                or rank.shape[0] != sets):
+            raise ValueError("expected %d x %d coefficients, %d positions and %d rank rows"
+                             % (sets, self.coeff_numel, self.coeff_numel, sets))
+        M = int(n_iter) + 1
+        if out is None:
+            out = torch.empty((sets * M,) + self.rec_shape, dtype=torch.float32, device=flat.device)
+        row_max = torch.empty(sets * M, dtype=torch.float32, device=flat.device) if want_max else None
+        ws = None
+        n = int(lib.wam_waverec1_ranked_workspace_bytes(self._h, sets, n_iter, route))
+        if n:
+            ws = self._ws.get("ranked1")
+            if ws is None or ws.numel() < n:
+                ws = self._ws["ranked1"] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib.wam_waverec1_ranked(self._h, sets, ptr(flat), ptr(rank), rank.shape[1], ptr(pos), n_iter, n_comp,
+                                      int(bool(deletion)), route, ptr(out), ptr(row_max), ptr(ws),
+                                      stream_of(flat.device)))
+        return out, row_max
+
     def waverec_bf16_nhwc(self, flat, batch, channels, alphas=None, out=None):
         """flat band-major coefficients of `batch` planes (images x channels) -> the reconstruction as
         bf16 images [n_alpha * batch / channels, channels, *rec_shape] in channels_last memory (the
@@ -362,6 +399,20 @@ def noise_add(x, sigma, n_samples, items, item_stride, noised_len, seed=0, sampl
                                ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), sample_base, item_base, ptr(out),
                                stream_of(x.device)))
     return out
+
+
+def peak_divide(x, row_max, zero_silent=False, out=None):
+    """x [rows, len] float32 / row_max [rows] (wam_peak_divide; in place without `out`) -> (out, silent
+    int32 [rows]: row_max == 0). zero_silent: a silent row is left as it is."""
+    require_cuda(x, "x")
+    rows, length = x.shape
+    if not x.is_contiguous() or row_max.numel() != rows or row_max.dtype != torch.float32:
+        raise ValueError("peak_divide: contiguous [rows, len] rows and %d float32 maxima" % rows)
+    out = x if out is None else out
+    silent = torch.empty(rows, dtype=torch.int32, device=x.device)
+    check(lib.wam_peak_divide(rows, length, ptr(x), ptr(row_max), ptr(out), ptr(silent), int(bool(zero_silent)),
+                              stream_of(x.device)))
+    return out, silent
 
 
 def subband_maps(plan, coeff_grads, groups, group_items, channels, maps=None, band_max=None, want_max=True):

@@ -402,130 +402,117 @@ int wam_peak_normalize(int64_t rows, int64_t len, const float* in, float* out, i
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Insertion / deletion of voxel WAMs (Eval3DWAM; an addition, the reference evaluates no volumes):
- * the n_iter + 1 masked reconstructions of every volume in one call. The selection rule, the layout of
- * coeffs, rank and pos and the pad rule are those of wam_rank_mask_coeffs above, for a 3D plan:
- * mask m of set s keeps the coefficient at per-item offset k when (rank[s, pos[k]] < thr(m)) !=
- * (deletion != 0), a pos[k] of -1 or outside [0, rank_len) reading as rank -1; a kept value is
- * multiplied by 1.0f and a dropped one by 0.0f, the approximation like any other band.
- * out [sets * (n_iter + 1), *rec_shape] float32: volume s * (n_iter + 1) + m = wam_waverec of set s
- * masked by m. Two routes compute it, bit-identical to each other:
+ * Ranked synthesis: the n_iter + 1 masked reconstructions of every item straight from a ranking, in one
+ * call. wam_waverec_ranked serves 3D plans only, wam_waverec2_ranked 2D plans and wam_waverec1_ranked 1D
+ * plans; the three share one implementation and the contract of this section, and each block below states
+ * its layout, its route 1 and its differences only.
+ * Selection. The rule, the layout of coeffs, rank and pos and the pad rule are exactly those of
+ * wam_rank_mask_coeffs: thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len; mask m of
+ * an item keeps the coefficient at per-item offset k when (rank[row, pos[k]] < thr(m)) != (deletion != 0),
+ * row being the item's rank row; a pos[k] of -1 or outside [0, rank_len) reads as rank -1 (kept by every
+ * mask under insertion, dropped by every mask under deletion); two coefficients may share a slot; a kept
+ * value is multiplied by 1.0f and a dropped one by 0.0f (a dropped negative value is -0.0f, a dropped NaN
+ * stays NaN), the approximation like any other band. coeffs: band-major coefficients as wam_wavedec
+ * writes them; rank [rows, rank_len] int32 (device); pos [K] int32 (device), K = wam_plan_coeff_numel,
+ * shared by all items. Output item (item, m) = wam_waverec of the item masked by m.
+ * Routes. Two routes compute the output, bit-identical to each other:
  *   route 0: the masked sets are written band-major into the workspace (what wam_rank_mask_coeffs
- *     writes, over the 1 + 7 * levels bands) and wam_waverec reads them: every 3D plan, any alignment;
- *   route 1: 3D Haar plans with levels <= 2 and dimensions divisible by 2^levels whose wam_waverec runs
- *     the fused block kernel (not WAM_PLAN_GENERIC): the threshold is applied as the synthesis loads
- *     its coefficients, nothing is stored in between and no workspace is read. It needs out 16-byte
- *     and coeffs and pos 8-byte aligned.
+ *     writes, over all bands of the plan) and the plan's wam_waverec reads them, whatever route its
+ *     synthesis takes: every plan of the entry's dimension, any alignment of coeffs, rank, pos and out.
+ *     Workspace: the (n_iter + 1) * K floats of every item, rounded up to 16 bytes, followed by
+ *     wam_plan_workspace_bytes(plan, output items);
+ *   route 1: a fused kernel applies the threshold as the synthesis loads its coefficients; no masked
+ *     coefficient is stored. The plans it serves and the pointers it takes are stated per dimension;
+ *   route -1: the plan's own route, which wam_waverec*_ranked_route returns: 1 wherever route 1 serves the
+ *     plan, else 0. The route queries work on host-only plans and are negative for a NULL plan or a plan
+ *     of another dimension.
+ * Fallback. Forcing route 1 on a plan it does not serve returns WAM_ERR_UNSUPPORTED and launches nothing;
+ * forcing it with pointers it cannot take returns WAM_ERR_UNSUPPORTED. With route -1 a call that route 1
+ * cannot take runs route 0 in the same workspace.
+ * Errors. A plan of another dimension: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG: a NULL plan, coeffs, rank,
+ * pos or out, a negative item count, rank_len < 1 or > INT32_MAX, n_iter < 1, n_comp < 0, a host-only
+ * plan, another route value, more than 65535 * 16 masks on route 0, and a NULL or misaligned (16 bytes)
+ * workspace where the route reads one; nothing is launched then. An item count of 0 returns WAM_OK, with
+ * any workspace. The *_workspace_bytes queries return 0 for invalid arguments.
  * ---------------------------------------------------------------------------------------------- */
-/* the route a plan takes by itself: 0 = expansion + wam_waverec (any 3D plan), 1 = fused Haar kernel
- * (where it applies; the faster one there, profiles/eval3d_kbench.txt). Works on host-only plans;
- * negative for a NULL or non-3D plan. */
+
+/* ---- 3D: insertion / deletion of voxel WAMs (Eval3DWAM; an addition, the reference evaluates no
+ * volumes). One rank row per set. out [sets * (n_iter + 1), *rec_shape] float32: volume s * (n_iter + 1) + m.
+ *   route 0 expands over the 1 + 7 * levels bands;
+ *   route 1: 3D Haar plans with levels <= 2 and dimensions divisible by 2^levels whose wam_waverec runs
+ *     the fused block kernel (not WAM_PLAN_GENERIC); no workspace is read. It needs out 16-byte and
+ *     coeffs and pos 8-byte aligned. */
+/* the route a plan takes by itself: 1 = the fused Haar kernel where it applies (the faster one there,
+ * profiles/eval3d_kbench.txt) */
 int    wam_waverec_ranked_route(const wam_plan* plan);
-/* bytes of workspace wam_waverec_ranked needs on `route` (-1: the plan's own): route 1 none; route 0
- * sets * (n_iter + 1) * wam_plan_coeff_numel floats, rounded up to 16 bytes, followed by
- * wam_plan_workspace_bytes(plan, sets * (n_iter + 1)). 0 for invalid arguments. */
+/* bytes of workspace wam_waverec_ranked needs on `route`: route 1 none; route 0 as above; -1 (the plan's
+ * own) the own route's size, 0 where it is route 1 */
 size_t wam_waverec_ranked_workspace_bytes(const wam_plan* plan, int64_t sets, int64_t n_iter, int route);
-/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
- * wam_waverec_ranked_workspace_bytes(plan, sets, n_iter, 0) bytes on route 0, not read on route 1 (may
- * be NULL). Forcing route 1 on a plan it does not serve, or with pointers it cannot take, returns
- * WAM_ERR_UNSUPPORTED; with route -1 a call whose pointers route 1 cannot take runs route 0 when a
- * workspace is given. A non-3D plan: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG as for
- * wam_rank_mask_coeffs (a NULL plan, coeffs, rank, pos or out, sets < 0, rank_len < 1 or > INT32_MAX,
- * n_iter < 1, n_comp < 0), for a host-only plan, another route value, more than 65535 * 16 masks, and
- * for a NULL or misaligned workspace on route 0; nothing is launched then. sets == 0 returns WAM_OK. */
+/* workspace (device, 16-byte aligned): at least wam_waverec_ranked_workspace_bytes(plan, sets, n_iter, 0)
+ * bytes on route 0, not read on route 1 (may be NULL). With route -1 a call whose pointers route 1 cannot
+ * take runs route 0 when a workspace is given, and returns WAM_ERR_UNSUPPORTED without one. A NULL or
+ * misaligned workspace is WAM_ERR_INVALID_ARG on route 0 only. More than 65535 * 16 masks is
+ * WAM_ERR_INVALID_ARG on either route. */
 int    wam_waverec_ranked(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
                           int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
                           int route /* -1: the plan's own */, float* out /* [sets*(n_iter+1), *rec_shape] */,
                           void* workspace, void* stream);
 
-/* ------------------------------------------------------------------------------------------------
- * Insertion / deletion of image WAMs by ranking (Eval2DWAM with mask_layout="mosaic"): the
- * n_iter + 1 masked reconstructions of every image's channel planes in one call. wam_waverec_ranked
- * above stays 3D-only; these are the entries of 2D plans. The selection rule is wam_rank_mask_coeffs's:
- * thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len; mask m of image n keeps the
- * coefficient at per-plane offset k when (rank[n, pos[k]] < thr(m)) != (deletion != 0), a pos[k] of -1
- * or outside [0, rank_len) reading as rank -1; a kept value is multiplied by 1.0f and a dropped one by
- * 0.0f (a dropped negative value is -0.0f, a dropped NaN stays NaN), the approximation like any band.
- * coeffs: band-major coefficients of images * channels planes as wam_wavedec writes them, plane (n, c)
- * = n * channels + c (wam_threshold_mask_coeffs's layout). rank [images, rank_len] int32 (device), one
- * ranking per image shared by its channels. pos [K] int32 (device), K = wam_plan_coeff_numel, shared by
- * all planes. out [images, n_iter + 1, channels, rec_h, rec_w] float32: image n, mask m is a contiguous
- * [channels, rec_h, rec_w] block. Two routes compute it, bit-identical to each other:
- *   route 0: the masked sets are written band-major into the workspace (planes (n, m, c), the mask
- *     expansion of wam_rank_mask_coeffs over the 1 + 3 * levels bands) and wam_waverec reads them,
- *     whatever route the plan's synthesis takes: every 2D plan, any alignment of coeffs, pos and out;
+/* ---- 2D: insertion / deletion of image WAMs by ranking (Eval2DWAM with mask_layout="mosaic"). The
+ * items are images * channels planes, channels in 1..4; coeffs holds plane (n, c) = n * channels + c
+ * (wam_threshold_mask_coeffs's layout); rank [images, rank_len]: one ranking per image shared by its
+ * channels. out [images, n_iter + 1, channels, rec_h, rec_w] float32: image n, mask m is a contiguous
+ * [channels, rec_h, rec_w] block.
+ *   route 0 expands over the 1 + 3 * levels bands into planes (n, m, c);
  *   route 1: plans whose wam_waverec runs the plane-resident synthesis (filters up to 8 taps whose
  *     levels fit its LDS, not WAM_PLAN_GENERIC / WAM_PLAN_NO_PLANE): a pre-pass writes the ranking in
  *     coefficient order once per image (images * K int32 of workspace), and the synthesis applies the
- *     threshold as it loads its coefficient rows; no masked coefficient is stored. It needs out 8-byte
- *     aligned (its pixel pairs are 8-byte stores); coeffs, rank and pos need only their natural 4.
- * ---------------------------------------------------------------------------------------------- */
-/* the route a plan takes by itself: 0 = expansion + wam_waverec, 1 = the fused plane-resident kernel
- * (only where it measured faster, profiles/eval2d_kbench.txt). Works on host-only plans; negative for
- * a NULL or non-2D plan. */
+ *     threshold as it loads its coefficient rows. It needs out 8-byte aligned (its pixel pairs are
+ *     8-byte stores); coeffs, rank and pos need only their natural 4. */
+/* the route a plan takes by itself: 1 = the fused plane-resident kernel (only where it measured faster,
+ * profiles/eval2d_kbench.txt) */
 int    wam_waverec2_ranked_route(const wam_plan* plan);
 /* bytes of workspace wam_waverec2_ranked needs on `route`: route 1 the rank table, images * K int32
- * rounded up to 16 bytes; route 0 images * (n_iter + 1) * channels * K floats, rounded up to 16 bytes,
- * followed by wam_plan_workspace_bytes(plan, images * (n_iter + 1) * channels); -1 (the plan's own)
- * route 0's size, which is the fallback's and holds route 1's table too. 0 for invalid arguments. */
+ * rounded up to 16 bytes; route 0 as above over images * channels planes; -1 (the plan's own) route 0's
+ * size, which is the fallback's and holds route 1's table too. 0 also for channels outside 1..4. */
 size_t wam_waverec2_ranked_workspace_bytes(const wam_plan* plan, int64_t images, int channels, int64_t n_iter,
                                            int route);
-/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
- * wam_waverec2_ranked_workspace_bytes(plan, images, channels, n_iter, route) bytes. Forcing route 1 on a
- * plan it does not serve, or with an `out` it cannot take, returns WAM_ERR_UNSUPPORTED; with route -1 a
- * call whose pointers route 1 cannot take runs route 0. A non-2D plan: WAM_ERR_UNSUPPORTED.
- * WAM_ERR_INVALID_ARG: a NULL plan, coeffs, rank, pos or out, images < 0, channels outside 1..4,
- * rank_len < 1 or > INT32_MAX, n_iter < 1, n_comp < 0, a host-only plan, another route value, a NULL or
- * misaligned workspace, more than 65535 * 16 masks on route 0 or more than INT32_MAX (plane, mask)
- * pairs on route 1; nothing is launched then. images == 0 returns WAM_OK. */
+/* workspace (device, 16-byte aligned): at least wam_waverec2_ranked_workspace_bytes(plan, images,
+ * channels, n_iter, route) bytes on every route; a NULL or misaligned one is WAM_ERR_INVALID_ARG. Also
+ * WAM_ERR_INVALID_ARG: channels outside 1..4, and more than INT32_MAX (plane, mask) pairs on route 1 (the
+ * one error found after a launch: the rank table is already written then). */
 int    wam_waverec2_ranked(const wam_plan* plan, int64_t images, int channels, const float* coeffs,
                            const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
                            int64_t n_comp, int deletion, int route /* -1: the plan's own */,
                            float* out /* [images, n_iter+1, channels, rec_h, rec_w] */, void* workspace,
                            void* stream);
 
-/* ------------------------------------------------------------------------------------------------
- * Insertion / deletion of audio WAMs with every coefficient ranked by its own gradient
- * (Eval1DWAM with mask_layout="coeffs"): the n_iter + 1 masked reconstructions of every clip and their
- * peak values in one call, then the division. These are the entries of 1D plans. The selection rule,
- * the layout of coeffs, rank and pos and the pad rule are exactly those of wam_rank_mask_coeffs:
- * thr(0) = 0, thr(m) = min(m * n_comp, rank_len), thr(n_iter) = rank_len; mask m of set s keeps the
- * coefficient at per-item offset k when (rank[s, pos[k]] < thr(m)) != (deletion != 0), a pos[k] of -1 or
- * outside [0, rank_len) reading as rank -1 (kept by every mask under insertion, dropped by every mask
- * under deletion); two coefficients may share a slot; a kept value is multiplied by 1.0f and a dropped
- * one by 0.0f, the approximation like any other band. out [sets * (n_iter + 1), rec_len] float32,
- * rec_len = wam_plan_rec_shape: row s * (n_iter + 1) + m = wam_waverec of set s masked by m.
- * row_max [sets * (n_iter + 1)] float32 (device, may be NULL): row_max[r] = the signed maximum of out row
- * r over rec_len, bit-equal to the maximum wam_peak_normalize reduces, a zero maximum written as
- * +0.0f; inputs are finite, as in wam_peak_normalize's contract. Two routes compute both, bit-identical
- * to each other in out and in row_max:
- *   route 0: the masked sets are written band-major into the workspace (wam_rank_mask_coeffs), the
- *     plan's wam_waverec reads them, and a max-only reduction pass fills row_max when it is given: every
- *     1D plan, any alignment of coeffs, rank, pos and out;
+/* ---- 1D: insertion / deletion of audio WAMs with every coefficient ranked by its own gradient
+ * (Eval1DWAM with mask_layout="coeffs"): the reconstructions and their peak values in one call, then the
+ * division (wam_peak_divide). One rank row per set. out [sets * (n_iter + 1), rec_len] float32, rec_len =
+ * wam_plan_rec_shape: row s * (n_iter + 1) + m. row_max [sets * (n_iter + 1)] float32 (device, may be
+ * NULL): row_max[r] = the signed maximum of out row r over rec_len, bit-equal to the maximum
+ * wam_peak_normalize reduces, a zero maximum written as +0.0f; inputs are finite, as in
+ * wam_peak_normalize's contract. The two routes are bit-identical in out and in row_max.
+ *   route 0 expands over the 1 + levels bands, and a max-only reduction pass fills row_max when it is
+ *     given;
  *   route 1: plans whose wam_waverec runs the persistent fused tile kernel on every tile (filters up to
  *     20 taps, levels <= 8, the register and LDS footprint of that kernel, a non-periodic mode, not
  *     WAM_PLAN_GENERIC; an (L, levels) whose ranked kernel would spill registers is excluded too --
  *     none is today): a pre-pass writes the ranking in coefficient order once per set (sets * K int32 of
- *     workspace), and the synthesis applies the threshold as it stages its coefficients; no masked
- *     coefficient is stored and each workgroup adds the maximum of the outputs it wrote to row_max with
- *     one atomic (row_max is set to -inf first; the maximum does not depend on the order). Any alignment.
- * ---------------------------------------------------------------------------------------------- */
-/* the route a plan takes by itself: 0 = expansion + wam_waverec (+ maxima), 1 = the fused tile kernel
- * wherever it applies (its slowest round beat route 0's fastest at every filter length from 2 to 20 taps,
- * profiles/eval1d_ranked_kbench.txt). Works on host-only plans; negative for a NULL or non-1D plan. */
+ *     workspace), and the synthesis applies the threshold as it stages its coefficients; each workgroup
+ *     adds the maximum of the outputs it wrote to row_max with one atomic (row_max is set to -inf first;
+ *     the maximum does not depend on the order). Any alignment. */
+/* the route a plan takes by itself: 1 = the fused tile kernel wherever it applies (its slowest round beat
+ * route 0's fastest at every filter length from 2 to 20 taps, profiles/eval1d_ranked_kbench.txt) */
 int    wam_waverec1_ranked_route(const wam_plan* plan);
 /* bytes of workspace wam_waverec1_ranked needs on `route`: route 1 the rank table, sets * K int32 rounded
- * up to 16 bytes; route 0 sets * (n_iter + 1) * K floats, rounded up to 16 bytes, followed by
- * wam_plan_workspace_bytes(plan, sets * (n_iter + 1)); -1 (the plan's own) route 0's size, which is the
- * fallback's and holds route 1's table too. 0 for invalid arguments. */
+ * up to 16 bytes; route 0 as above; -1 (the plan's own) route 0's size, which is the fallback's and holds
+ * route 1's table too */
 size_t wam_waverec1_ranked_workspace_bytes(const wam_plan* plan, int64_t sets, int64_t n_iter, int route);
-/* route: 0, 1 or -1 (the plan's own). workspace (device, 16-byte aligned): at least
- * wam_waverec1_ranked_workspace_bytes(plan, sets, n_iter, route) bytes. Forcing route 1 on a plan it does
- * not serve returns WAM_ERR_UNSUPPORTED and launches nothing; with route -1 a call that route 1 cannot
- * take runs route 0. A non-1D plan: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG as for wam_waverec_ranked (a
- * NULL plan, coeffs, rank, pos or out, sets < 0, rank_len < 1 or > INT32_MAX, n_iter < 1, n_comp < 0, a
- * host-only plan, another route value, more than 65535 * 16 masks), for more than INT32_MAX output rows
- * and for a NULL or misaligned workspace; nothing is launched then. sets == 0 returns WAM_OK. */
+/* workspace (device, 16-byte aligned): at least wam_waverec1_ranked_workspace_bytes(plan, sets, n_iter,
+ * route) bytes on every route; a NULL or misaligned one is WAM_ERR_INVALID_ARG. Also WAM_ERR_INVALID_ARG,
+ * on either route and before any launch: more than 65535 * 16 masks, more than INT32_MAX output rows. */
 int    wam_waverec1_ranked(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* rank,
                            int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
                            int route /* -1: the plan's own */, float* out /* [sets*(n_iter+1), rec_len] */,

@@ -6,7 +6,7 @@ flags from the same coefficients and ranking (the identity slot map of mask_layo
 
   composition  wam_rank_mask_coeffs -> wam_waverec -> wam_peak_normalize (in place): the parent's kernels
   route 0      wam_waverec1_ranked(route 0): the same expansion and synthesis, a max-only pass -> wam_peak_divide
-  route 1      wam_waverec1_ranked(route 1): k_rank_table1 -> k_dwt1_syn_ranked, no masked coefficient stored,
+  route 1      wam_waverec1_ranked(route 1): k_rank_table -> k_dwt1_syn_ranked, no masked coefficient stored,
                the maxima from the kernel's own reduction -> wam_peak_divide
 
 Per geometry the contenders alternate over --rounds rounds; each round times --window seconds of calls per

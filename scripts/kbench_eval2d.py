@@ -1,11 +1,11 @@
-"""wam_waverec2_ranked (wam_amd/csrc/evaluate2d.hip) beside the composition Eval2DWAM ran before it, on the
+"""wam_waverec2_ranked (wam_amd/csrc/evaluate_ranked.hip) beside the composition Eval2DWAM ran before it, on the
 same tree, at the evaluation geometry of the headline configurations: 224 x 224 images of 3 channels,
 n_iter = 64 (65 reconstructions per image), haar J=3 and db4 J=3, for 1 and 4 images. Three contenders
 compute the same [images, 65, 3, 224, 224] reconstructions from the same coefficients, ranking and mosaic
 slot map (frames.wam_cell_source, the held slot appended):
 
   composition  per image wam_rank_masks -> wam_coeff_masks -> wam_waverec: the float masks are stored
-  route 0      k_rank_mask2 (the shared mask expansion) into the workspace -> wam_waverec
+  route 0      k_rank_mask (the shared mask expansion, timer label "k_rank_mask2") into the workspace -> wam_waverec
   route 1      k_rank_table -> k_plane_syn_ranked: no masked coefficient is stored
 
 Per geometry the contenders alternate over --rounds rounds; each round times --window seconds of calls per

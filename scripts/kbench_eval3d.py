@@ -1,4 +1,4 @@
-"""The two routes of wam_waverec_ranked (wam_amd/csrc/evaluate3d.hip) on the same tree, at c5's evaluation
+"""The two routes of wam_waverec_ranked (wam_amd/csrc/evaluate_ranked.hip) on the same tree, at c5's evaluation
 geometry -- haar J=2 on 128^3 volumes, n_iter = 64, so 65 reconstructions per volume, for 1 and 4 volumes
 -- and at J=1. Route 0 is the mask expansion (k_rank_mask over the plan's bands) into a workspace followed
 by wam_waverec, i.e. the kernels the tree had before the fused one; route 1 is k_haar3_syn_ranked.

@@ -1288,7 +1288,7 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
 }
 
 // ------------------------------------------------------------------------------------------------
-// The fused route of wam_waverec1_ranked (evaluate1d.hip): plans whose wam_waverec runs
+// The fused route of wam_waverec1_ranked (evaluate_ranked.hip): plans whose wam_waverec runs
 // k_dwt1_syn_int on every tile. The ranked kernel keeps a rank beside every prefetched coefficient
 // (2 * nslots registers); every (L, J) k_dwt1_syn_int takes compiles without scratch.
 bool dwt1_syn_ranked_supported(const wam_plan* p) {

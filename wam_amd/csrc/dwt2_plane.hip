@@ -952,25 +952,14 @@ __global__ void __launch_bounds__(kPT) __attribute__((amdgpu_waves_per_eu(4, 8))
 // of the mask expansion applied as syn_stream's coefficient rows enter its ring (SynKeepRank), so
 // the M = n_iter + 1 masked coefficient sets of a plane are never written. One workgroup per (plane,
 // mask), mask-fastest: the masks of one plane share an XCD, its coefficient reads and its rank reads.
-// rtab [images, K] int32: the rank of every coefficient's mask slot in coefficient order (k_rank_table),
-// read at the coefficient's own offset. out [images, M, channels, oh, ow], plane = image * channels +
-// channel. g.batch = planes, g.n_alpha = M.
+// rtab [images, K] int32: the rank of every coefficient's mask slot in coefficient order (k_rank_table,
+// evaluate_ranked.hip), read at the coefficient's own offset. out [images, M, channels, oh, ow], plane =
+// image * channels + channel. g.batch = planes, g.n_alpha = M.
 struct RankedArgs {
   const int32_t* rtab;
   int64_t K, rank_len, n_iter, n_comp;
   int channels, deletion;
 };
-
-__global__ void __launch_bounds__(256) k_rank_table(int64_t images, int64_t K, const int32_t* __restrict__ rank,
-                                                    int64_t rank_len, const int32_t* __restrict__ pos,
-                                                    int32_t* __restrict__ rtab) {
-  const int64_t total = images * K;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t n = t / K;
-    const int32_t p = pos[t - n * K];
-    rtab[t] = ((uint64_t)(int64_t)p < (uint64_t)rank_len) ? rank[n * rank_len + p] : -1;
-  }
-}
 
 template <int L>
 __global__ void __launch_bounds__(kPT) __attribute__((amdgpu_waves_per_eu(4, 8)))
@@ -1342,29 +1331,19 @@ int launch_dwt2_plane_synthesis(const wam_plan* p, int64_t batch, const float* c
   return WAM_OK;
 }
 
-// The fused route of wam_waverec2_ranked: the rank table in coefficient order (rtab, images * K
-// int32 of the caller's workspace), then one (plane, mask) workgroup each. Declines
-// (WAM_ERR_UNSUPPORTED) a plan k_plane_syn does not serve and pointers its accesses cannot take: the
-// float2 output stores want `out` 8-byte aligned.
-int64_t dwt2_plane_ranked_table_bytes(const wam_plan* p, int64_t images) {
-  return (images * p->band_off[p->nbands] * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;
-}
-
+// The fused route of wam_waverec2_ranked: one (plane, mask) workgroup each, reading the rank table in
+// coefficient order (rtab, images * K int32, filled by the caller). Declines (WAM_ERR_UNSUPPORTED) a plan
+// k_plane_syn does not serve and pointers its accesses cannot take: the float2 output stores want `out`
+// 8-byte aligned.
 int launch_dwt2_plane_synthesis_ranked(const wam_plan* p, int64_t images, int channels, const float* coeffs,
-                                       const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
-                                       int64_t n_comp, int deletion, float* out, int32_t* rtab, hipStream_t st) {
+                                       const int32_t* rtab, int64_t rank_len, int64_t n_iter, int64_t n_comp,
+                                       int deletion, float* out, hipStream_t st) {
   if (!syn_ok(p) || ((uintptr_t)out & 7) || !rtab || ((uintptr_t)rtab & 3)) return WAM_ERR_UNSUPPORTED;
   const int64_t planes = images * channels, M = n_iter + 1, K = p->band_off[p->nbands];
   if (M > INT32_MAX || planes > INT32_MAX / M) return WAM_ERR_INVALID_ARG;  // one workgroup per (plane, mask)
   SynGeom g = make_syn_geom(p, planes);
   g.n_alpha = (int)M;
   const int lds_bytes = syn_lds_floats(p, g.lcap, g.scap) * 4;
-  {
-    WamTimer tm(st, "k_rank_table", 4.0 * (images * (double)rank_len + K + 2.0 * images * K));
-    hipLaunchKernelGGL(k_rank_table, dim3(wam_grid(images * K, 256)), dim3(256), 0, st, images, K, rank, rank_len, pos,
-                       rtab);
-    WAM_LAUNCH_CHECK();
-  }
   const RankedArgs ra{rtab, K, rank_len, n_iter, n_comp, channels, deletion};
   const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;
   // algorithmic bytes: coefficients and ranks once, every reconstruction once

@@ -186,28 +186,24 @@ int launch_dwt3_haar_analysis_noisy(const wam_plan* p, int64_t batch, const floa
 int launch_dwt3_haar_synthesis(const wam_plan* p, int64_t batch, const float* coeffs, const float* alpha, int n_alpha,
                                float* out, hipStream_t st);
 
-// wam_waverec_ranked (evaluate3d.hip). Route 1: the rank threshold applied on the synthesis load
-// (dwt3_haar.hip), out = sets * (n_iter + 1) volumes, nothing in between. Route 0's first half: the
-// masked coefficient sets through the shared mask_expand skeleton (evaluate1d.hip), any 3D plan.
+// The fused routes of the ranked syntheses (evaluate_ranked.hip): the rank threshold of the mask
+// expansion applied as the synthesis loads its coefficients, nothing stored in between. Each declines
+// (WAM_ERR_UNSUPPORTED, nothing launched) a plan or pointers its kernel cannot take. rtab [items, K]
+// int32: the ranks in coefficient order, filled by the caller (k_rank_table).
+// 3D (dwt3_haar.hip): out = sets * (n_iter + 1) volumes, ranks read through pos
 int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
                                       int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp,
                                       int deletion, float* out, hipStream_t st);
-int launch_rank_mask_coeffs3(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
-                             int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp, int deletion,
-                             float* out, hipStream_t st);
-
-// wam_waverec1_ranked (evaluate1d.hip), route 1: k_dwt1_syn_int with the rank threshold applied as a
-// unit's coefficients are staged (dwt1_tile.hip). rtab [sets, K] int32: the ranks in coefficient order
-// (evaluate1d.hip writes it). out [sets * (n_iter + 1), rec_len]; row_max (may be NULL) must hold -inf.
+// 1D (dwt1_tile.hip): k_dwt1_syn_int with the threshold applied as a unit's coefficients are staged.
+// out [sets * (n_iter + 1), rec_len]; row_max (may be NULL) must hold -inf.
 bool dwt1_syn_ranked_supported(const wam_plan* p);
 int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rtab,
                                       int64_t rank_len, int64_t n_iter, int64_t n_comp, int deletion, float* out,
                                       float* row_max, hipStream_t st);
-
-// wam_waverec2_ranked (evaluate2d.hip), route 1: k_plane_syn with the rank threshold applied as the
-// coefficient rows are loaded (dwt2_plane.hip). rtab: dwt2_plane_ranked_table_bytes of workspace, the
-// ranks in coefficient order. out [images, n_iter + 1, channels, rec_h, rec_w].
-int64_t dwt2_plane_ranked_table_bytes(const wam_plan* p, int64_t images);
+// 2D (dwt2_plane.hip): k_plane_syn with the threshold applied as the coefficient rows are loaded.
+// out [images, n_iter + 1, channels, rec_h, rec_w].
 int launch_dwt2_plane_synthesis_ranked(const wam_plan* p, int64_t images, int channels, const float* coeffs,
-                                       const int32_t* rank, int64_t rank_len, const int32_t* pos, int64_t n_iter,
-                                       int64_t n_comp, int deletion, float* out, int32_t* rtab, hipStream_t st);
+                                       const int32_t* rtab, int64_t rank_len, int64_t n_iter, int64_t n_comp,
+                                       int deletion, float* out, hipStream_t st);
+// 1D route 0's maxima pass beside k_peak_normalize (evaluate1d.hip): row_max[r] = max of row r of in [rows, len]
+int launch_row_max(int64_t rows, int64_t len, const float* in, float* row_max, hipStream_t st);

@@ -1,4 +1,4 @@
-// The masked expansion shared by the evaluators' band-major mask kernels (evaluate1d.hip: k_rank_mask,
+// The masked expansion shared by the evaluators' band-major mask kernels (rankmask.hpp: k_rank_mask,
 // analyze2d.hip: k_threshold_mask): every coefficient of every input item is read once and written,
 // times a 0 / 1 multiplier, into all the mask items wam_waverec reads -- the masks are never stored.
 // mask_thr, kMaskChunk and aligned16 / aligned4 also serve baselines2d.hip and evaluate.hip.

@@ -110,48 +110,62 @@ class Plan:
                               stream_of(flat.device)))
         return out
 
+    # ---- ranked synthesis (evaluate_ranked.hip): one helper behind the 3D, 2D and 1D entries
+    def _ranked_route(self, sym):
+        r = getattr(lib, sym + "_route")(self._h)
+        if r < 0:
+            check(-r)
+        return r
+
+    def _waverec_ranked(self, sym, key, dims, flat, rank, pos, n_iter, n_comp, deletion, route, out, lead=None,
+                        want_max=None):
+        """lib.<sym> and its workspace query. dims: the entry's leading counts, (sets,) or (images, channels);
+        rank holds dims[0] rows. key: the workspace's slot in the plan's cache. lead: the leading dims of a
+        new `out`, (items * (n_iter + 1),) unless given. want_max None: the entry takes no row_max.
+        Returns (out, row_max)."""
+        require_cuda(flat, "coefficients")
+        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
+        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise TypeError("wam_amd: rank and pos must be int32")
+        items = int(np.prod(dims))
+        if (flat.numel() != items * self.coeff_numel or pos.numel() != self.coeff_numel or rank.dim() != 2
+                or rank.shape[0] != dims[0]):
+            raise ValueError("expected %s x %d coefficients, %d positions and %d rank rows"
+                             % (" x ".join(map(str, dims)), self.coeff_numel, self.coeff_numel, dims[0]))
+        M = int(n_iter) + 1
+        if out is None:
+            out = torch.empty((lead or (items * M,)) + self.rec_shape, dtype=torch.float32, device=flat.device)
+        row_max = torch.empty(items * M, dtype=torch.float32, device=flat.device) if want_max else None
+        ws = None
+        # 3D: the plan's own route keeps a workspace at hand only when it is route 0
+        n = int(getattr(lib, sym + "_workspace_bytes")(self._h, *dims, n_iter, route))
+        if n:
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() < n:
+                ws = self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        extra = () if want_max is None else (ptr(row_max),)
+        check(getattr(lib, sym)(self._h, *dims, ptr(flat), ptr(rank), rank.shape[1], ptr(pos), n_iter, n_comp,
+                                int(bool(deletion)), route, ptr(out), *extra, ptr(ws), stream_of(flat.device)))
+        return out, row_max
+
     @property
     def ranked_route(self):
         """The route waverec_ranked takes by itself (wam_waverec_ranked_route): 0 = mask expansion +
         waverec, 1 = the fused 3D Haar kernel. 3D plans only."""
-        r = lib.wam_waverec_ranked_route(self._h)
-        if r < 0:
-            check(-r)
-        return r
+        return self._ranked_route("wam_waverec_ranked")
 
     def waverec_ranked(self, flat, sets, rank, pos, n_iter, n_comp, deletion, route=-1, out=None):
         """The n_iter + 1 masked reconstructions of each of `sets` volumes (wam_waverec_ranked): flat
         band-major coefficients of the sets, rank int32 [sets, rank_len] and pos int32 [coeff_numel] as
         for wam_rank_mask_coeffs -> [sets * (n_iter + 1), *rec_shape], volume s * (n_iter + 1) + m.
         route: -1 the plan's own, 0 expansion + waverec (workspace from the plan), 1 the fused kernel."""
-        require_cuda(flat, "coefficients")
-        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
-        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
-            raise TypeError("wam_amd: rank and pos must be int32")
-        if flat.numel() != sets * self.coeff_numel or pos.numel() != self.coeff_numel or rank.shape[0] != sets:
-            raise ValueError("expected %d x %d coefficients, %d positions and %d rank rows"
-                             % (sets, self.coeff_numel, self.coeff_numel, sets))
-        M = int(n_iter) + 1
-        if out is None:
-            out = torch.empty((sets * M,) + self.rec_shape, dtype=torch.float32, device=flat.device)
-        ws = None
-        # the plan's own route keeps a workspace at hand only when it is route 0
-        n = int(lib.wam_waverec_ranked_workspace_bytes(self._h, sets, n_iter, route))
-        if n:
-            ws = self._ws.get("ranked")
-            if ws is None or ws.numel() < n:
-                ws = self._ws["ranked"] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        check(lib.wam_waverec_ranked(self._h, sets, ptr(flat), ptr(rank), rank.shape[1], ptr(pos), n_iter, n_comp,
-                                     int(bool(deletion)), route, ptr(out), ptr(ws), stream_of(flat.device)))
-        return out
+        return self._waverec_ranked("wam_waverec_ranked", "ranked", (sets,), flat, rank, pos, n_iter, n_comp,
+                                    deletion, route, out)[0]
 
     def ranked2_route(self):
         """The route waverec2_ranked takes by itself (wam_waverec2_ranked_route): 0 = mask expansion +
         waverec, 1 = the fused plane-resident kernel. 2D plans only."""
-        r = lib.wam_waverec2_ranked_route(self._h)
-        if r < 0:
-            check(-r)
-        return r
+        return self._ranked_route("wam_waverec2_ranked")
 
     def waverec2_ranked(self, flat, images, channels, rank, pos, n_iter, n_comp, deletion, route=-1, out=None):
         """The n_iter + 1 masked reconstructions of each of `images` images of `channels` planes
@@ -159,35 +173,13 @@ class Plan:
         [images, rank_len] and pos int32 [coeff_numel] -> [images, n_iter + 1, channels, *rec_shape].
         route: -1 the plan's own, 0 expansion + waverec, 1 the fused kernel; the workspace of either comes
         from the plan."""
-        require_cuda(flat, "coefficients")
-        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
-        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
-            raise TypeError("wam_amd: rank and pos must be int32")
-        if (flat.numel() != images * channels * self.coeff_numel or pos.numel() != self.coeff_numel
-                or rank.dim() != 2 or rank.shape[0] != images):
-            raise ValueError("expected %d x %d x %d coefficients, %d positions and %d rank rows"
-                             % (images, channels, self.coeff_numel, self.coeff_numel, images))
-        M = int(n_iter) + 1
-        if out is None:
-            out = torch.empty((images, M, channels) + self.rec_shape, dtype=torch.float32, device=flat.device)
-        ws = None
-        n = int(lib.wam_waverec2_ranked_workspace_bytes(self._h, images, channels, n_iter, route))
-        if n:
-            ws = self._ws.get("ranked2")
-            if ws is None or ws.numel() < n:
-                ws = self._ws["ranked2"] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        check(lib.wam_waverec2_ranked(self._h, images, channels, ptr(flat), ptr(rank), rank.shape[1], ptr(pos),
-                                      n_iter, n_comp, int(bool(deletion)), route, ptr(out), ptr(ws),
-                                      stream_of(flat.device)))
-        return out
+        return self._waverec_ranked("wam_waverec2_ranked", "ranked2", (images, channels), flat, rank, pos, n_iter,
+                                    n_comp, deletion, route, out, lead=(images, int(n_iter) + 1, channels))[0]
 
     def ranked1_route(self):
         """The route waverec1_ranked takes by itself (wam_waverec1_ranked_route): 0 = mask expansion +
         waverec, 1 = the fused tile kernel. 1D plans only."""
-        r = lib.wam_waverec1_ranked_route(self._h)
-        if r < 0:
-            check(-r)
-        return r
+        return self._ranked_route("wam_waverec1_ranked")
 
     def waverec1_ranked(self, flat, sets, rank, pos, n_iter, n_comp, deletion, route=-1, out=None, want_max=True):
         """The n_iter + 1 masked reconstructions of each of `sets` signals and their signed maxima
@@ -195,28 +187,8 @@ class Plan:
         pos int32 [coeff_numel] as for wam_rank_mask_coeffs -> (out [sets * (n_iter + 1), rec_len],
         row_max [sets * (n_iter + 1)] or None without want_max). route: -1 the plan's own, 0 expansion +
         waverec, 1 the fused kernel; the workspace of either comes from the plan."""
-        require_cuda(flat, "coefficients")
-        flat, rank, pos = flat.contiguous(), rank.contiguous(), pos.contiguous()
-        if rank.dtype != torch.int32 or pos.dtype != torch.int32:
-            raise TypeError("wam_amd: rank and pos must be int32")
-        if (flat.numel() != sets * self.coeff_numel or pos.numel() != self.coeff_numel or rank.dim() != 2
-                or rank.shape[0] != sets):
-            raise ValueError("expected %d x %d coefficients, %d positions and %d rank rows"
-                             % (sets, self.coeff_numel, self.coeff_numel, sets))
-        M = int(n_iter) + 1
-        if out is None:
-            out = torch.empty((sets * M,) + self.rec_shape, dtype=torch.float32, device=flat.device)
-        row_max = torch.empty(sets * M, dtype=torch.float32, device=flat.device) if want_max else None
-        ws = None
-        n = int(lib.wam_waverec1_ranked_workspace_bytes(self._h, sets, n_iter, route))
-        if n:
-            ws = self._ws.get("ranked1")
-            if ws is None or ws.numel() < n:
-                ws = self._ws["ranked1"] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        check(lib.wam_waverec1_ranked(self._h, sets, ptr(flat), ptr(rank), rank.shape[1], ptr(pos), n_iter, n_comp,
-                                      int(bool(deletion)), route, ptr(out), ptr(row_max), ptr(ws),
-                                      stream_of(flat.device)))
-        return out, row_max
+        return self._waverec_ranked("wam_waverec1_ranked", "ranked1", (sets,), flat, rank, pos, n_iter, n_comp,
+                                    deletion, route, out, want_max=bool(want_max))
 
     def waverec_bf16_nhwc(self, flat, batch, channels, alphas=None, out=None):
         """flat band-major coefficients of `batch` planes (images x channels) -> the reconstruction as

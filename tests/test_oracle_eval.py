@@ -54,14 +54,29 @@ def test_zoom_map_and_gaussian(G):
     assert np.allclose(gaussian_filter(wam, sigma=2), G["gauss"], rtol=1e-14, atol=1e-15)
 
 
-@pytest.mark.parametrize("wav,size,J", [("haar", 224, 3), ("db2", 224, 3), ("db4", 96, 2), ("sym4", 64, 1)])
+@pytest.mark.parametrize("grid,hw", [(5, (15, 17)), (7, (37, 52)), (28, (244, 244)), (8, (61, 100)), (3, (2, 11))])
+def test_zoom_cell_map_gathers_what_scipy_zooms(grid, hw):
+    """masks gathered through zoom_cell_map == scipy's zoom(order=0) of the float masks themselves, on
+    ragged and non-square canvases (also a down-scale)."""
+    from scipy.ndimage import zoom
+    from wam_amd.evaluation import zoom_cell_map
+    masks = np.random.RandomState(grid).standard_normal((4, grid, grid)).astype(np.float32)
+    cell = zoom_cell_map(grid, hw)
+    assert cell.shape == hw and cell.min() >= 0 and cell.max() < grid * grid
+    got = masks.reshape(4, -1)[:, cell.reshape(-1)].reshape((4,) + hw)
+    assert np.array_equal(got, zoom(masks, (1, hw[0] / grid, hw[1] / grid), order=0))
+
+
+@pytest.mark.parametrize("wav,size,J", [("haar", 224, 3), ("db2", 224, 3), ("db4", 96, 2), ("sym4", 64, 1),
+                                        ("db2", (40, 56), 2), ("db4", (37, 52), 2), ("haar", (24, 40), 3),
+                                        ("sym4", (33, 20), 1)])
 def test_coeff_array_positions(wav, size, J):
     """The GPU path's per-coefficient positions reproduce pywt.coeffs_to_array (via the oracle)."""
     from wam_amd.evaluation import coeff_array_layout
 
     class P:  # band layout of a plan without a device
         pass
-    x = np.random.RandomState(5).standard_normal((size, size))
+    x = np.random.RandomState(5).standard_normal(size if isinstance(size, tuple) else (size, size))
     c = dwt.wavedec2(x, wav, J, mode="symmetric")
     bands = [c[0]] + [t for lv in c[1:] for t in lv]
     p = P()

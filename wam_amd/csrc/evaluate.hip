@@ -130,6 +130,10 @@ struct GaussW {
 template <int AXIS>
 __global__ void __launch_bounds__(256) k_gauss_pass(int64_t items, int h, int w, int radius, GaussW gw,
                                                     const double* __restrict__ in, double* __restrict__ out) {
+  // hipcc contracts a multiply into a following add by default, also through __dmul_rn / __dadd_rn (inline
+  // functions of the headers, outside this pragma's reach): plain operators under contract(off) keep the
+  // product and the sum rounded separately, which is what holds the result to scipy's bits
+#pragma clang fp contract(off)
   const int64_t plane = (int64_t)h * w;
   const int64_t total = items * plane;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -141,8 +145,8 @@ __global__ void __launch_bounds__(256) k_gauss_pass(int64_t items, int h, int w,
       if (AXIS == 0) return x[(int64_t)wam_ext_index(r + d, h, WAM_MODE_SYMMETRIC) * w + c];
       return x[(int64_t)r * w + wam_ext_index(c + d, w, WAM_MODE_SYMMETRIC)];
     };
-    double acc = __dmul_rn(at(0), gw.w[0]);
-    for (int j = radius; j >= 1; --j) acc = __dadd_rn(acc, __dmul_rn(__dadd_rn(at(-j), at(j)), gw.w[j]));
+    double acc = at(0) * gw.w[0];
+    for (int j = radius; j >= 1; --j) acc = acc + (at(-j) + at(j)) * gw.w[j];
     out[t] = acc;
   }
 }

@@ -402,6 +402,69 @@ def test_trapz_f32(P, n, groups, f64):
         R.assert_within(host(acc), a64, bound, "trapz_f32_weighted " + tag)
 
 
+# ------------------------------------------------------------------------------ refusals
+def test_argument_errors_launch_nothing(P):
+    """The host checks of the seven accumulator entries, on 2 items, a frame of 5 pixels, 7
+    coefficients, 2 bands, 2 groups: every required pointer NULL in turn, every checked count
+    negative, normalize without band_max, the cube's mode 3 / mode 1 without weights / mode 2 without
+    prev, wam_trapz_f32 without an accumulator or sequential without the accumulator's own prev all
+    return WAM_ERR_INVALID_ARG; zero groups and zero work return WAM_OK; and no output buffer
+    (filled with 7) changes a bit. Valid arguments would change them: the maps are all ones."""
+    from wam_amd._lib import lib, ptr, stream_of
+    OK, INVALID = 0, 1
+    n, F, K, nb, G = 2, 5, 7, 2, 2
+    i32 = lambda *v: dev(np.array(v, np.int32))
+    src, band = i32(3, -1, 0, 6, 2), i32(1, 0, 0, 1, 0)                     # pixel -> coefficient, its band
+    dst, cband = i32(2, -1, 4, 0, -1, -1, 3), i32(0, 0, 0, 1, 1, 1, 1)      # the same mosaic, coefficient -> pixel
+    ones = lambda *shape: torch.ones(shape, device="cuda")
+    maps, bmax, w, stream = ones(G * n, K), ones(G, nb), ones(G), ones(G, n * F)
+    outs = {k: torch.full((n * F,), 7.0, dtype=dt, device="cuda")
+            for k, dt in (("frame", torch.float64), ("prev", torch.float32), ("acc", torch.float32),
+                          ("prev64", torch.float64), ("acc64", torch.float64))}
+    st = stream_of(maps.device)
+
+    def entry(fn, order, **defaults):
+        def call(**kw):
+            a = dict(defaults, **kw)
+            return fn(*[a[k] if isinstance(a[k], (int, float)) else ptr(a[k]) for k in order.split()], st)
+        return call
+
+    pix = dict(groups=G, k0=0, n=n, F=F, src=src, band=band, maps=maps, K=K, bmax=bmax, nb=nb, norm=1, w=None, **outs)
+    coef = dict(pix, dst=dst, cband=cband)
+    cube = dict(groups=G, k0=0, n=n, L=F, src=src, maps=maps, K=K, mode=2, n_total=25.0, w=w, **outs)
+    flat = dict(groups=G, k0=0, len=n * F, src=stream, scale=25.0, w=None, **outs)
+    # entry, its required pointers, its checked counts, further refusals, calls with nothing to do
+    table = [
+        (entry(lib.wam_frame_accumulate, "groups n F src band maps K bmax nb norm frame", **pix),
+         "src band maps frame", "groups n F", [{"bmax": None}], [{"groups": 0}, {"n": 0}, {"F": 0}]),
+        (entry(lib.wam_frame_accumulate_coef, "groups n K F dst cband maps bmax nb norm frame", **coef),
+         "dst cband maps frame", "groups n K F", [{"bmax": None}], [{"groups": 0}, {"n": 0}, {"K": 0}]),
+        (entry(lib.wam_frame_trapz, "groups k0 n F src band maps K bmax nb norm w prev acc", **pix),
+         "src band maps prev acc", "groups n F", [{"bmax": None}, {"bmax": None, "w": w}],
+         [{"groups": 0}, {"n": 0}, {"F": 0}]),
+        (entry(lib.wam_frame_trapz_coef, "groups k0 n K F dst cband maps bmax nb norm w prev acc", **coef),
+         "dst cband maps prev acc", "groups n K F", [{"bmax": None}, {"bmax": None, "w": w}],
+         [{"groups": 0}, {"n": 0}, {"K": 0}]),
+        (entry(lib.wam_cube_accumulate, "groups k0 n L src maps K mode n_total w prev acc", **cube),
+         "src maps acc", "groups n L", [{"mode": 3}, {"mode": -1}, {"mode": 1, "w": None}, {"mode": 2, "prev": None}],
+         [{"groups": 0}, {"n": 0}, {"L": 0}, {"groups": 0, "mode": 0, "prev": None}]),
+        (entry(lib.wam_accumulate_f32, "groups len src scale acc", **flat),
+         "src acc", "groups len", [], [{"len": 0}, {"groups": 0, "scale": 0.0}]),   # no groups: acc / scale alone
+        (entry(lib.wam_trapz_f32, "groups k0 len src w prev acc prev64 acc64", **flat),
+         "src", "groups len", [{"acc": None, "acc64": None}, {"prev": None, "acc64": None}, {"prev64": None},
+                               {"acc": None, "prev": None, "prev64": None}],
+         [{"len": 0}, {"groups": 0}, {"len": 0, "acc64": None}, {"groups": 0, "w": w, "prev": None, "prev64": None}]),
+    ]
+    for call, pointers, counts, refused, nothing in table:
+        for kw in [{k: None} for k in pointers.split()] + [{k: -1} for k in counts.split()] + refused:
+            assert call(**kw) == INVALID, kw
+        for kw in nothing:
+            assert call(**kw) == OK, kw
+    torch.cuda.synchronize()
+    for k, t in outs.items():
+        assert bool((t == 7.0).all()), k
+
+
 # ------------------------------------------------------------------------------ sigma
 @pytest.mark.parametrize("offset", [0, 1])
 @pytest.mark.parametrize("items,stride,length", [(3, 1001, 999), (5, 4096, 4096), (1, 7, 7), (2, 40000, 37),

@@ -309,6 +309,61 @@ __global__ void __launch_bounds__(256) k_subband_maps(BandTable bt, int64_t item
   }
 }
 
+// ------------------------------------------------------------------------------ accumulator pieces
+// What the nine accumulators share. The order contract, stated once: a result element is updated
+// sample by sample (group s of the launch is step k0 + s of the call chain), each step one fixed
+// sequence of IEEE operations -- the reference accumulates sample by sample, and the
+// coefficient-order kernels must give the pixel-order kernels' bits. Loads may be issued ahead in
+// blocks; the arithmetic never leaves sample order. The weighted product is one fused multiply-add
+// (fmaf / fma); the sequential trapezoid is an add, a halving and an add (the halving is exact).
+__device__ __forceinline__ float nan_to_num(float v) {
+  if (v != v) return 0.f;
+  if (isinf(v)) return v > 0 ? 3.4028234663852886e+38f : -3.4028234663852886e+38f;
+  return v;
+}
+
+// The mosaic kernels' sample loop: f(s, map value, band maximum or 1) for s = 0 .. groups - 1 in
+// order, the 16 loads of a block of 8 samples issued together before the block's first f, then a
+// scalar tail. mp: the element's map value of sample 0, mstride: floats between samples.
+template <class F>
+__device__ __forceinline__ void for_samples(int64_t groups, const float* __restrict__ mp, int64_t mstride,
+                                            const float* __restrict__ band_max, int n_bands, int32_t b,
+                                            int normalize, F f) {
+  int64_t s = 0;
+  for (; s + 8 <= groups; s += 8) {
+    float v[8], m[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      v[u] = mp[(s + u) * mstride];
+      m[u] = normalize ? band_max[(s + u) * n_bands + b] : 1.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) f(s + u, v[u], m[u]);
+  }
+  for (; s < groups; ++s) f(s, mp[s * mstride], normalize ? band_max[s * n_bands + b] : 1.f);
+}
+
+// One IG step on an fp32 or fp64 accumulator: weighted (a += w[s] v, prev untouched) or the
+// sequential trapezoid, whose first step of the chain (k0 + s == 0) only records v.
+template <class T>
+__device__ __forceinline__ void trapz_step(T& a, T& pv, T v, const float* __restrict__ weights, int64_t s,
+                                           int64_t k0) {
+  if (weights) {
+    a = fma((T)weights[s], v, a);
+  } else {
+    if (k0 + s > 0) a = a + (pv + v) / (T)2;
+    pv = v;
+  }
+}
+
+// One cube step: mode 0 the legacy running average, 1 weighted, 2 the trapezoid of nan_to_num(v)
+__device__ __forceinline__ void cube_step(float& a, float& pv, float v, int mode, float n_total,
+                                          const float* __restrict__ weights, int64_t s, int64_t k0) {
+  if (mode == 0) a = (a + v) / n_total;
+  else if (mode == 1) a = fmaf(weights[s], v, a);
+  else trapz_step<float>(a, pv, nan_to_num(v), nullptr, s, k0);
+}
+
 // ------------------------------------------------------------------------------ frame accumulate
 __global__ void __launch_bounds__(256) k_frame_accumulate(int64_t groups, int64_t group_items, int64_t frame_len,
                                                           const int32_t* __restrict__ src,
@@ -324,26 +379,8 @@ __global__ void __launch_bounds__(256) k_frame_accumulate(int64_t groups, int64_
     if (sidx < 0) continue;
     const int32_t b = band[p];
     double acc = frame[t];
-    // samples in blocks of 8: the block's loads are issued together, the fp64 sum stays in
-    // sample order (the reference accumulates sample by sample)
-    const float* mp = maps + n * maps_item_len + sidx;
-    const int64_t mstride = group_items * maps_item_len;
-    int64_t s = 0;
-    for (; s + 8 <= groups; s += 8) {
-      float v[8], m[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        v[u] = mp[(s + u) * mstride];
-        m[u] = normalize ? band_max[(s + u) * n_bands + b] : 1.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc += (double)(normalize ? v[u] / m[u] : v[u]);
-    }
-    for (; s < groups; ++s) {
-      float v = mp[s * mstride];
-      if (normalize) v = v / band_max[s * n_bands + b];
-      acc += (double)v;
-    }
+    for_samples(groups, maps + n * maps_item_len + sidx, group_items * maps_item_len, band_max, n_bands, b, normalize,
+                [&](int64_t, float v, float m) { acc += (double)(normalize ? v / m : v); });
     frame[t] = acc;
   }
 }
@@ -376,32 +413,11 @@ __global__ void __launch_bounds__(256) k_frame_accumulate_coef(int64_t groups, i
     for (int64_t n = r * items_per_thread; n < n1; ++n) {
       double* fp = frame + n * frame_len + d;
       double acc = *fp;
-      const float* mp = maps + n * maps_item_len + k;
-      int64_t s = 0;
-      for (; s + 8 <= groups; s += 8) {
-        float v[8], m[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          v[u] = mp[(s + u) * mstride];
-          m[u] = normalize ? band_max[(s + u) * n_bands + b] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += (double)(normalize ? v[u] / m[u] : v[u]);
-      }
-      for (; s < groups; ++s) {
-        float v = mp[s * mstride];
-        if (normalize) v = v / band_max[s * n_bands + b];
-        acc += (double)v;
-      }
+      for_samples(groups, maps + n * maps_item_len + k, mstride, band_max, n_bands, b, normalize,
+                  [&](int64_t, float v, float m) { acc += (double)(normalize ? v / m : v); });
       *fp = acc;
     }
   }
-}
-
-__device__ __forceinline__ float nan_to_num(float v) {
-  if (v != v) return 0.f;
-  if (isinf(v)) return v > 0 ? 3.4028234663852886e+38f : -3.4028234663852886e+38f;
-  return v;
 }
 
 __global__ void __launch_bounds__(256) k_frame_trapz(int64_t groups, int64_t k0, int64_t group_items, int64_t frame_len,
@@ -418,32 +434,12 @@ __global__ void __launch_bounds__(256) k_frame_trapz(int64_t groups, int64_t k0,
     const int32_t b = sidx >= 0 ? band[p] : 0;  // pixels outside the mosaic load a valid dummy
     float a = acc[t];
     float pv = prev[t];
-    // loads in blocks of 8 steps (issued together), the trapezoid / weighted sum in step order
-    const float* mp = maps + n * maps_item_len + (sidx >= 0 ? sidx : 0);
-    const int64_t mstride = group_items * maps_item_len;
-    auto step = [&](int64_t s, float v, float m) {
-      if (sidx < 0) v = 0.f;
-      else if (normalize) v = v / m;
-      v = nan_to_num(v);
-      if (weights) {
-        a = fmaf(weights[s], v, a);
-      } else {
-        if (k0 + s > 0) a = a + (pv + v) / 2.0f;
-        pv = v;
-      }
-    };
-    int64_t s = 0;
-    for (; s + 8 <= groups; s += 8) {
-      float v[8], m[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        v[u] = mp[(s + u) * mstride];
-        m[u] = normalize ? band_max[(s + u) * n_bands + b] : 1.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) step(s + u, v[u], m[u]);
-    }
-    for (; s < groups; ++s) step(s, mp[s * mstride], normalize ? band_max[s * n_bands + b] : 1.f);
+    for_samples(groups, maps + n * maps_item_len + (sidx >= 0 ? sidx : 0), group_items * maps_item_len, band_max,
+                n_bands, b, normalize, [&](int64_t s, float v, float m) {
+                  if (sidx < 0) v = 0.f;
+                  else if (normalize) v = v / m;
+                  trapz_step<float>(a, pv, nan_to_num(v), weights, s, k0);
+                });
     acc[t] = a;
     prev[t] = pv;
   }
@@ -480,33 +476,39 @@ __global__ void __launch_bounds__(256) k_frame_trapz_coef(int64_t groups, int64_
       const int64_t fi = n * frame_len + d;
       float a = acc[fi];
       float pv = prev[fi];
-      const float* mp = maps + n * maps_item_len + k;
-      auto step = [&](int64_t s, float v, float m) {
-        if (normalize) v = v / m;
-        v = nan_to_num(v);
-        if (weights) {
-          a = fmaf(weights[s], v, a);
-        } else {
-          if (k0 + s > 0) a = a + (pv + v) / 2.0f;
-          pv = v;
-        }
-      };
-      int64_t s = 0;
-      for (; s + 8 <= groups; s += 8) {
-        float v[8], m[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          v[u] = mp[(s + u) * mstride];
-          m[u] = normalize ? band_max[(s + u) * n_bands + b] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) step(s + u, v[u], m[u]);
-      }
-      for (; s < groups; ++s) step(s, mp[s * mstride], normalize ? band_max[s * n_bands + b] : 1.f);
+      for_samples(groups, maps + n * maps_item_len + k, mstride, band_max, n_bands, b, normalize,
+                  [&](int64_t s, float v, float m) {
+                    if (normalize) v = v / m;
+                    trapz_step<float>(a, pv, nan_to_num(v), weights, s, k0);
+                  });
       acc[fi] = a;
       prev[fi] = pv;
     }
   }
+}
+
+// Host side of the four wam_frame_* entries. walk_len is the length the threads walk beside the
+// items: frame_len in pixel order, maps_item_len in coefficient order.
+bool frame_args_ok(int64_t groups, int64_t group_items, int64_t walk_len, int64_t frame_len, bool pointers,
+                   int normalize, const float* band_max) {
+  return groups >= 0 && group_items >= 0 && walk_len >= 0 && frame_len >= 0 && pointers && (!normalize || band_max);
+}
+
+// algorithmic bytes of either order
+double frame_bytes(int64_t groups, int64_t group_items, int64_t frame_len) {
+  return 4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len;
+}
+
+// Coefficient order: mosaic tables beyond ~2 MB (8 B per coefficient; 512^2 planes) would be
+// re-read from HBM per item, so each thread then takes a run of items of one coefficient, the runs
+// sized for about target_threads threads; small tables stay in L2 and every (item, coefficient)
+// gets its own thread. The accumulation runs at ~1 M threads. The trapezoid runs at ~4 M: c4 (128
+// images x 293 K coefficients) takes 9 items per thread -- PMC/algorithmic 1.058 and 929 us per
+// 21-step launch, against 1.066 / 1,007 us at ~1 M threads and 1.133 / 1,066 us at one item per
+// thread (profiles/r05o_trapz_runs_ab.log)
+int64_t coef_items_per_thread(int64_t maps_item_len, int64_t group_items, int64_t work, int64_t target_threads) {
+  const int64_t ipt = maps_item_len * 8 > (int64_t(2) << 20) ? work / target_threads : 1;
+  return ipt < 1 ? 1 : (ipt > group_items ? group_items : ipt);
 }
 
 // cube: value = |g| from item-major maps (channels = 1); see wam_cube_accumulate
@@ -522,18 +524,9 @@ __global__ void __launch_bounds__(256) k_cube_accumulate(int64_t groups, int64_t
     const int32_t sidx = src[p];
     float a = acc[t];
     float pv = prev ? prev[t] : 0.f;
-    for (int64_t s = 0; s < groups; ++s) {
-      float v = sidx >= 0 ? maps[(s * group_items + n) * maps_item_len + sidx] : 0.f;
-      if (mode == 0) {
-        a = (a + v) / n_total;
-      } else if (mode == 1) {
-        a = fmaf(weights[s], v, a);
-      } else {
-        v = nan_to_num(v);
-        if (k0 + s > 0) a = a + (pv + v) / 2.0f;
-        pv = v;
-      }
-    }
+    for (int64_t s = 0; s < groups; ++s)
+      cube_step(a, pv, sidx >= 0 ? maps[(s * group_items + n) * maps_item_len + sidx] : 0.f, mode, n_total, weights, s,
+                k0);
     acc[t] = a;
     if (prev) prev[t] = pv;
   }
@@ -592,18 +585,8 @@ __global__ void __launch_bounds__(256) k_cube_accumulate4(int64_t groups, int64_
       for (int u = 0; u < 4; ++u) {
         if (s + u >= groups) break;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float x = sv[e] >= 0 ? v[u][e] : 0.f;
-          if (mode == 0) {
-            a[e] = (a[e] + x) / n_total;
-          } else if (mode == 1) {
-            a[e] = fmaf(weights[s + u], x, a[e]);
-          } else {
-            x = nan_to_num(x);
-            if (k0 + s + u > 0) a[e] = a[e] + (pv[e] + x) / 2.0f;
-            pv[e] = x;
-          }
-        }
+        for (int e = 0; e < 4; ++e)
+          cube_step(a[e], pv[e], sv[e] >= 0 ? v[u][e] : 0.f, mode, n_total, weights, s + u, k0);
       }
     }
     if constexpr (STRIDED) {
@@ -629,38 +612,24 @@ __global__ void __launch_bounds__(256) k_accumulate_f32(int64_t groups, int64_t 
   }
 }
 
+// element e of k_trapz_f32 on an fp32 or fp64 accumulator (prev may be NULL when weighted)
+template <class T>
+__device__ __forceinline__ void trapz_element(int64_t groups, int64_t k0, int64_t len, int64_t e,
+                                              const float* __restrict__ src, const float* __restrict__ weights,
+                                              T* __restrict__ prev, T* __restrict__ acc) {
+  T a = acc[e], pv = prev ? prev[e] : (T)0;
+  for (int64_t s = 0; s < groups; ++s) trapz_step<T>(a, pv, (T)src[s * len + e], weights, s, k0);
+  acc[e] = a;
+  if (prev) prev[e] = pv;
+}
+
 __global__ void __launch_bounds__(256) k_trapz_f32(int64_t groups, int64_t k0, int64_t len, const float* __restrict__ src,
                                                    const float* __restrict__ weights, float* __restrict__ prev32,
                                                    float* __restrict__ acc32, double* __restrict__ prev64,
                                                    double* __restrict__ acc64) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < len; e += (int64_t)gridDim.x * blockDim.x) {
-    if (acc64) {
-      double a = acc64[e], pv = prev64 ? prev64[e] : 0.0;
-      for (int64_t s = 0; s < groups; ++s) {
-        double v = (double)src[s * len + e];
-        if (weights) {
-          a = fma((double)weights[s], v, a);
-        } else {
-          if (k0 + s > 0) a = a + (pv + v) / 2.0;
-          pv = v;
-        }
-      }
-      acc64[e] = a;
-      if (prev64) prev64[e] = pv;
-    } else {
-      float a = acc32[e], pv = prev32 ? prev32[e] : 0.f;
-      for (int64_t s = 0; s < groups; ++s) {
-        float v = src[s * len + e];
-        if (weights) {
-          a = fmaf(weights[s], v, a);
-        } else {
-          if (k0 + s > 0) a = a + (pv + v) / 2.0f;
-          pv = v;
-        }
-      }
-      acc32[e] = a;
-      if (prev32) prev32[e] = pv;
-    }
+    if (acc64) trapz_element(groups, k0, len, e, src, weights, prev64, acc64);
+    else trapz_element(groups, k0, len, e, src, weights, prev32, acc32);
   }
 }
 
@@ -809,12 +778,8 @@ int wam_item_sigma(int64_t items, int64_t item_stride, int64_t len, const float*
   if (items == 0) return WAM_OK;
   const bool vec4 = item_stride % 4 == 0 && len % 4 == 0 && (uintptr_t)x % 16 == 0;
   WamTimer tm((hipStream_t)stream, "k_item_sigma", 4.0 * (double)items * len);
-  if (vec4)
-    hipLaunchKernelGGL(k_item_sigma<true>, dim3((unsigned)items), dim3(1024), 0, (hipStream_t)stream, x, item_stride,
-                       len, spread, sigma);
-  else
-    hipLaunchKernelGGL(k_item_sigma<false>, dim3((unsigned)items), dim3(1024), 0, (hipStream_t)stream, x, item_stride,
-                       len, spread, sigma);
+  auto k = vec4 ? k_item_sigma<true> : k_item_sigma<false>;
+  hipLaunchKernelGGL(k, dim3((unsigned)items), dim3(1024), 0, (hipStream_t)stream, x, item_stride, len, spread, sigma);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -843,13 +808,9 @@ int wam_item_sigma_ws(int64_t items, int64_t item_stride, int64_t len, const flo
   float2* part = reinterpret_cast<float2*>(ws);
   unsigned int* cnt = reinterpret_cast<unsigned int*>(part + items * chunks);
   WamTimer tm((hipStream_t)stream, "k_item_sigma", 4.0 * (double)items * len);
-  const dim3 grid((unsigned)(items * chunks));
-  if (vec4)
-    hipLaunchKernelGGL(k_item_sigma_split<true>, grid, dim3(kSigT), 0, (hipStream_t)stream, x, item_stride, len, chunk,
-                       chunks, spread, sigma, part, cnt);
-  else
-    hipLaunchKernelGGL(k_item_sigma_split<false>, grid, dim3(kSigT), 0, (hipStream_t)stream, x, item_stride, len,
-                       chunk, chunks, spread, sigma, part, cnt);
+  auto k = vec4 ? k_item_sigma_split<true> : k_item_sigma_split<false>;
+  hipLaunchKernelGGL(k, dim3((unsigned)(items * chunks)), dim3(kSigT), 0, (hipStream_t)stream, x, item_stride, len,
+                     chunk, chunks, spread, sigma, part, cnt);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -864,15 +825,12 @@ int wam_noise_add_ex(int64_t n_samples, int64_t items, int64_t item_stride, int6
   if (work == 0) return WAM_OK;
   WamTimer tm((hipStream_t)stream, item_stride % 4 == 0 ? "k_noise_add<v4>" : "k_noise_add",
               4.0 * (double)items * item_stride * (1 + n_samples * (host_noise ? 2 : 1)));
-  if (item_stride % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-      (!host_noise || (uintptr_t)host_noise % 16 == 0))
-    hipLaunchKernelGGL(k_noise_add<true>, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, n_samples,
-                       items, item_stride, noised_len, x, sigma, host_noise, (uint32_t)seed, (uint32_t)(seed >> 32),
-                       sample_base, item_base, out);
-  else
-    hipLaunchKernelGGL(k_noise_add<false>, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, n_samples,
-                       items, item_stride, noised_len, x, sigma, host_noise, (uint32_t)seed, (uint32_t)(seed >> 32),
-                       sample_base, item_base, out);
+  const bool vec4 = item_stride % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
+                    (!host_noise || (uintptr_t)host_noise % 16 == 0);
+  auto k = vec4 ? k_noise_add<true> : k_noise_add<false>;
+  hipLaunchKernelGGL(k, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, n_samples, items, item_stride,
+                     noised_len, x, sigma, host_noise, (uint32_t)seed, (uint32_t)(seed >> 32), sample_base, item_base,
+                     out);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -901,12 +859,9 @@ int wam_subband_maps(const wam_plan* p, int64_t groups, int64_t group_items, int
   WamTimer tm((hipStream_t)stream, "k_subband_maps", 4.0 * (double)items * (channels + 1) * p->band_off[p->nbands]);
   bool vec4 = ((uintptr_t)coeff_grads & 15) == 0 && ((uintptr_t)maps & 15) == 0;
   for (int b = 0; b <= p->nbands; ++b) vec4 = vec4 && (p->band_off[b] % 4 == 0);
-  if (vec4)
-    hipLaunchKernelGGL(k_subband_maps<true>, dim3((unsigned)tiles, (unsigned)items), dim3(256), 0,
-                       (hipStream_t)stream, bt, items, group_items, channels, coeff_grads, maps, band_max);
-  else
-    hipLaunchKernelGGL(k_subband_maps<false>, dim3((unsigned)tiles, (unsigned)items), dim3(256), 0,
-                       (hipStream_t)stream, bt, items, group_items, channels, coeff_grads, maps, band_max);
+  auto k = vec4 ? k_subband_maps<true> : k_subband_maps<false>;
+  hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)items), dim3(256), 0, (hipStream_t)stream, bt, items,
+                     group_items, channels, coeff_grads, maps, band_max);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -914,12 +869,11 @@ int wam_subband_maps(const wam_plan* p, int64_t groups, int64_t group_items, int
 int wam_frame_accumulate(int64_t groups, int64_t group_items, int64_t frame_len, const int32_t* src,
                          const int32_t* band, const float* maps, int64_t maps_item_len, const float* band_max,
                          int n_bands, int normalize, double* frame, void* stream) {
-  if (groups < 0 || group_items < 0 || frame_len < 0 || !src || !band || !maps || !frame) return WAM_ERR_INVALID_ARG;
-  if (normalize && !band_max) return WAM_ERR_INVALID_ARG;
-  int64_t work = group_items * frame_len;
+  if (!frame_args_ok(groups, group_items, frame_len, frame_len, src && band && maps && frame, normalize, band_max))
+    return WAM_ERR_INVALID_ARG;
+  const int64_t work = group_items * frame_len;
   if (work == 0 || groups == 0) return WAM_OK;
-  WamTimer tm((hipStream_t)stream, "k_frame_accumulate",
-              4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len);
+  WamTimer tm((hipStream_t)stream, "k_frame_accumulate", frame_bytes(groups, group_items, frame_len));
   hipLaunchKernelGGL(k_frame_accumulate, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, groups,
                      group_items, frame_len, src, band, maps, maps_item_len, band_max, n_bands, normalize, frame);
   WAM_LAUNCH_CHECK();
@@ -929,18 +883,12 @@ int wam_frame_accumulate(int64_t groups, int64_t group_items, int64_t frame_len,
 int wam_frame_accumulate_coef(int64_t groups, int64_t group_items, int64_t maps_item_len, int64_t frame_len,
                               const int32_t* dst, const int32_t* cband, const float* maps, const float* band_max,
                               int n_bands, int normalize, double* frame, void* stream) {
-  if (groups < 0 || group_items < 0 || maps_item_len < 0 || frame_len < 0 || !dst || !cband || !maps || !frame)
+  if (!frame_args_ok(groups, group_items, maps_item_len, frame_len, dst && cband && maps && frame, normalize, band_max))
     return WAM_ERR_INVALID_ARG;
-  if (normalize && !band_max) return WAM_ERR_INVALID_ARG;
   const int64_t work = group_items * maps_item_len;
   if (work == 0 || groups == 0) return WAM_OK;
-  WamTimer tm((hipStream_t)stream, "k_frame_accumulate_coef",
-              4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len);
-  // mosaic tables beyond ~2 MB (8 B per coefficient; 512^2 planes) would be re-read from HBM per
-  // item: about a million threads then, each a run of items of one coefficient; small tables stay
-  // in L2 and every (item, coefficient) gets its own thread
-  int64_t ipt = maps_item_len * 8 > (int64_t(2) << 20) ? work / (int64_t(1) << 20) : 1;
-  ipt = ipt < 1 ? 1 : (ipt > group_items ? group_items : ipt);
+  WamTimer tm((hipStream_t)stream, "k_frame_accumulate_coef", frame_bytes(groups, group_items, frame_len));
+  const int64_t ipt = coef_items_per_thread(maps_item_len, group_items, work, int64_t(1) << 20);
   const int64_t threads = (group_items + ipt - 1) / ipt * maps_item_len;
   hipLaunchKernelGGL(k_frame_accumulate_coef, dim3(wam_grid(threads, 256)), dim3(256), 0, (hipStream_t)stream, groups,
                      group_items, maps_item_len, frame_len, dst, cband, maps, band_max, n_bands, normalize, ipt,
@@ -952,19 +900,13 @@ int wam_frame_accumulate_coef(int64_t groups, int64_t group_items, int64_t maps_
 int wam_frame_trapz_coef(int64_t groups, int64_t k0, int64_t group_items, int64_t maps_item_len, int64_t frame_len,
                          const int32_t* dst, const int32_t* cband, const float* maps, const float* band_max,
                          int n_bands, int normalize, const float* weights, float* prev, float* acc, void* stream) {
-  if (groups < 0 || group_items < 0 || maps_item_len < 0 || frame_len < 0 || !dst || !cband || !maps || !prev || !acc)
+  if (!frame_args_ok(groups, group_items, maps_item_len, frame_len, dst && cband && maps && prev && acc, normalize,
+                     band_max))
     return WAM_ERR_INVALID_ARG;
-  if (normalize && !band_max) return WAM_ERR_INVALID_ARG;
   const int64_t work = group_items * maps_item_len;
   if (work == 0 || groups == 0) return WAM_OK;
-  WamTimer tm((hipStream_t)stream, "k_frame_trapz_coef",
-              4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len);
-  // runs of items per thread when the mosaic tables outgrow L2 (as in wam_frame_accumulate_coef),
-  // sized for ~4 M threads: c4 (128 images x 293 K coefficients) runs 9 items per thread --
-  // PMC/algorithmic 1.058 and 929 us per 21-step launch, against 1.066 / 1,007 us at ~1 M threads
-  // and 1.133 / 1,066 us at one item per thread (profiles/r05o_trapz_runs_ab.log)
-  int64_t ipt = maps_item_len * 8 > (int64_t(2) << 20) ? work / (int64_t(1) << 22) : 1;
-  ipt = ipt < 1 ? 1 : (ipt > group_items ? group_items : ipt);
+  WamTimer tm((hipStream_t)stream, "k_frame_trapz_coef", frame_bytes(groups, group_items, frame_len));
+  const int64_t ipt = coef_items_per_thread(maps_item_len, group_items, work, int64_t(1) << 22);
   const int64_t threads = (group_items + ipt - 1) / ipt * maps_item_len;
   hipLaunchKernelGGL(k_frame_trapz_coef, dim3(wam_grid(threads, 256)), dim3(256), 0, (hipStream_t)stream, groups, k0,
                      group_items, maps_item_len, frame_len, dst, cband, maps, band_max, n_bands, normalize, weights,
@@ -976,13 +918,12 @@ int wam_frame_trapz_coef(int64_t groups, int64_t k0, int64_t group_items, int64_
 int wam_frame_trapz(int64_t groups, int64_t k0, int64_t group_items, int64_t frame_len, const int32_t* src,
                     const int32_t* band, const float* maps, int64_t maps_item_len, const float* band_max, int n_bands,
                     int normalize, const float* weights, float* prev, float* acc, void* stream) {
-  if (groups < 0 || group_items < 0 || frame_len < 0 || !src || !band || !maps || !prev || !acc)
+  if (!frame_args_ok(groups, group_items, frame_len, frame_len, src && band && maps && prev && acc, normalize,
+                     band_max))
     return WAM_ERR_INVALID_ARG;
-  if (normalize && !band_max) return WAM_ERR_INVALID_ARG;
-  int64_t work = group_items * frame_len;
+  const int64_t work = group_items * frame_len;
   if (work == 0 || groups == 0) return WAM_OK;
-  WamTimer tm((hipStream_t)stream, "k_frame_trapz",
-              4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len);
+  WamTimer tm((hipStream_t)stream, "k_frame_trapz", frame_bytes(groups, group_items, frame_len));
   hipLaunchKernelGGL(k_frame_trapz, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, groups, k0,
                      group_items, frame_len, src, band, maps, maps_item_len, band_max, n_bands, normalize, weights,
                      prev, acc);
@@ -1006,15 +947,9 @@ int wam_cube_accumulate(int64_t groups, int64_t k0, int64_t group_items, int64_t
                     ((uintptr_t)prev & 15) == 0;
   // strided (256-voxel wave blocks, work % 256 == 0): c5 154 -> 109 us per launch against the four
   // consecutive voxels per thread (profiles/r06zb_ab_cube_accumulate.log)
-  if (vec4 && work % 256 == 0)
-    hipLaunchKernelGGL(k_cube_accumulate4<true>, dim3(wam_grid(work / 4, 256)), dim3(256), 0, (hipStream_t)stream, groups,
-                       k0, group_items, cube_len, src, maps, maps_item_len, mode, n_total, weights, prev, acc);
-  else if (vec4)
-    hipLaunchKernelGGL(k_cube_accumulate4<false>, dim3(wam_grid(work / 4, 256)), dim3(256), 0, (hipStream_t)stream,
-                       groups, k0, group_items, cube_len, src, maps, maps_item_len, mode, n_total, weights, prev, acc);
-  else
-    hipLaunchKernelGGL(k_cube_accumulate, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, groups, k0,
-                       group_items, cube_len, src, maps, maps_item_len, mode, n_total, weights, prev, acc);
+  auto k = !vec4 ? k_cube_accumulate : work % 256 == 0 ? k_cube_accumulate4<true> : k_cube_accumulate4<false>;
+  hipLaunchKernelGGL(k, dim3(wam_grid(vec4 ? work / 4 : work, 256)), dim3(256), 0, (hipStream_t)stream, groups, k0,
+                     group_items, cube_len, src, maps, maps_item_len, mode, n_total, weights, prev, acc);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "dispatch.hpp"
 #include "kernels.hpp"
 #include "quantize.hpp"
 #include "rng.hpp"
@@ -970,16 +971,20 @@ __global__ void __launch_bounds__(kT1) k_dwt1_syn_ranked(const float* __restrict
 // ------------------------------------------------------------------------------------------------
 bool mode_ok(int mode) { return mode != WAM_MODE_PERIODIC; }
 
-// the persistent synthesis' register footprint and LDS for (L, J)
+// the persistent synthesis' register footprint and LDS for (L, J); false past 8 levels
 bool syn_int_fits(int L, int J) {
-#define WAM_SF(LL, JJ) \
-  if (L == LL && J == JJ) return SynShape<LL, JJ>::nslots <= 40 && SynShape<LL, JJ>::lds_bytes <= kLds1Cap;
-#define WAM_SFJ(LL) WAM_SF(LL, 1) WAM_SF(LL, 2) WAM_SF(LL, 3) WAM_SF(LL, 4) WAM_SF(LL, 5) WAM_SF(LL, 6) \
-                    WAM_SF(LL, 7) WAM_SF(LL, 8)
-  WAM_SFJ(2) WAM_SFJ(4) WAM_SFJ(6) WAM_SFJ(8) WAM_SFJ(10) WAM_SFJ(12) WAM_SFJ(14) WAM_SFJ(16) WAM_SFJ(18) WAM_SFJ(20)
-#undef WAM_SFJ
-#undef WAM_SF
-  return false;
+  return wam_dispatch_len_levels(WamLensEven20{}, L, J, [](auto l, auto j) -> int {
+    using Sh = SynShape<decltype(l)::value, decltype(j)::value>;
+    return Sh::nslots <= 40 && Sh::lds_bytes <= kLds1Cap ? WAM_OK : WAM_ERR_UNSUPPORTED;
+  }) == WAM_OK;
+}
+
+// (filter length, NOISE) of the analysis kernels
+template <class F>
+int dispatch_ln(int L, bool noise, F&& f) {
+  return wam_dispatch_len(WamLensEven20{}, L, [&](auto l) -> int {
+    return wam_dispatch_bool(noise, [&](auto nn) -> int { return f(l, nn); });
+  });
 }
 
 Dwt1Geom make_geom1(const wam_plan* p, int n, int mode, int64_t items) {
@@ -1082,7 +1087,7 @@ int syn_lds_bytes(const wam_plan* p) {
 }  // namespace
 
 bool dwt1_tile_supported(const wam_plan* p, bool adjoint) {
-  if (p->ndim != 1 || p->L > 20 || (p->L & 1)) return false;
+  if (p->ndim != 1 || !wam_len_in(WamLensEven20{}, p->L)) return false;
   if (!mode_ok(adjoint ? WAM_MODE_ZERO : p->mode)) return false;
   if (p->lin[0][0] > (1 << 30)) return false;
   const Dwt1Geom g = make_geom1(p, (int)(adjoint ? p->rec_shape[0] : p->lin[0][0]), adjoint ? WAM_MODE_ZERO : p->mode, 1);
@@ -1122,39 +1127,24 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
   const double bytes = nz ? 4.0 * ((double)nz->images * n + (double)batch * p->band_off[p->nbands])
                           : 4.0 * (double)batch * ((double)n + (double)p->band_off[p->nbands]);
   if (units > 0) {
-    int dev = 0;
-    WAM_HIP_CHECK(hipGetDevice(&dev));
     int cus = 256;
-    WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    WAM_HIP_CHECK(wam_device_cus(&cus));
     WamTimer tm(st, nz ? "k_dwt1_ana_int<noise>" : "k_dwt1_ana_int",
                 fold ? bytes : bytes * (double)(t_hi - t_lo) / g.tiles);
     // persistent grid: exactly the resident workgroups (VGPRs and LDS decide: 2 per CU for the
     // clean kernel's 107 VGPRs, 3 for the noisy one's 57 at c3's 51.5 KB of LDS), so no workgroup
     // waits for a slot and the units split evenly
-    switch (p->L) {
-#define WAM_D1AIN(LL, NN)                                                                                         \
-  {                                                                                                               \
-    if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana_int<LL, NN>, kLds1Cap)) return rc;                        \
-    int wgs = kAnaWgs;                                                                                            \
-    WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_dwt1_ana_int<LL, NN>, kT1, lds_i));         \
-    const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);                              \
-    hipLaunchKernelGGL((k_dwt1_ana_int<LL, NN>), dim3((unsigned)grid), dim3(kT1), lds_i, st, in, coeffs, filt, g, \
-                       t_lo, t_hi, units, NZ, S, fold);                                                           \
-  }
-#define WAM_D1AI(LL)                                                                                            \
-  case LL:                                                                                                      \
-    if (nz) {                                                                                                   \
-      WAM_D1AIN(LL, true)                                                                                       \
-    } else {                                                                                                    \
-      WAM_D1AIN(LL, false)                                                                                      \
-    }                                                                                                           \
-    break;
-      WAM_D1AI(2) WAM_D1AI(4) WAM_D1AI(6) WAM_D1AI(8) WAM_D1AI(10) WAM_D1AI(12) WAM_D1AI(14) WAM_D1AI(16)
-      WAM_D1AI(18) WAM_D1AI(20)
-#undef WAM_D1AI
-#undef WAM_D1AIN
-      default: return WAM_ERR_UNSUPPORTED;
-    }
+    if (int rc = dispatch_ln(p->L, nz != nullptr, [&](auto l, auto noise) -> int {
+          auto kern = k_dwt1_ana_int<decltype(l)::value, decltype(noise)::value>;
+          if (int rc = wam_lds_opt_in((const void*)kern, kLds1Cap)) return rc;
+          int wgs = kAnaWgs;
+          WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, kern, kT1, lds_i));
+          const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);
+          hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kT1), lds_i, st, in, coeffs, filt, g, t_lo, t_hi, units,
+                             NZ, S, fold);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   }
   // boundary tiles: persistent with window prefetch when every boundary window fits kPF * kT1
@@ -1166,53 +1156,28 @@ int launch_dwt1_tile_analysis(const wam_plan* p, int64_t batch, const float* in,
     max_wlen = std::max(max_wlen, 2 * (E[0] - S[0]) + pp);
   }
   if (nb_blocks > 0 && max_wlen <= kPF * kT1) {
-    int dev = 0;
-    WAM_HIP_CHECK(hipGetDevice(&dev));
     int cus = 256;
-    WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    WAM_HIP_CHECK(wam_device_cus(&cus));
     const int64_t grid = std::min<int64_t>(nb_blocks, (int64_t)kAnaWgs * cus);
     WamTimer tm(st, nz ? "k_dwt1_ana_p<noise>" : "k_dwt1_ana_p", bytes * (double)(g.tiles - (t_hi - t_lo)) / g.tiles);
-    switch (p->L) {
-#define WAM_D1APN(LL, NN)                                                                                      \
-  if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana_p<LL, NN>, kLds1Cap)) return rc;                            \
-  hipLaunchKernelGGL((k_dwt1_ana_p<LL, NN>), dim3((unsigned)grid), dim3(kT1), lds, st, in, coeffs, filt, g, t_lo, \
-                     t_hi, nb_blocks, NZ);
-#define WAM_D1AP(LL)                                                                                           \
-  case LL:                                                                                                     \
-    if (nz) {                                                                                                  \
-      WAM_D1APN(LL, true)                                                                                      \
-    } else {                                                                                                   \
-      WAM_D1APN(LL, false)                                                                                     \
-    }                                                                                                          \
-    break;
-      WAM_D1AP(2) WAM_D1AP(4) WAM_D1AP(6) WAM_D1AP(8) WAM_D1AP(10) WAM_D1AP(12) WAM_D1AP(14) WAM_D1AP(16)
-      WAM_D1AP(18) WAM_D1AP(20)
-#undef WAM_D1AP
-#undef WAM_D1APN
-      default: return WAM_ERR_UNSUPPORTED;
-    }
+    if (int rc = dispatch_ln(p->L, nz != nullptr, [&](auto l, auto noise) -> int {
+          auto kern = k_dwt1_ana_p<decltype(l)::value, decltype(noise)::value>;
+          if (int rc = wam_lds_opt_in((const void*)kern, kLds1Cap)) return rc;
+          hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kT1), lds, st, in, coeffs, filt, g, t_lo, t_hi, nb_blocks,
+                             NZ);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   } else if (nb_blocks > 0) {
     WamTimer tm(st, nz ? "k_dwt1_ana<noise>" : "k_dwt1_ana", bytes * (double)(g.tiles - (t_hi - t_lo)) / g.tiles);
-    switch (p->L) {
-#define WAM_D1AN(LL, NN)                                                                                     \
-  if (int rc = wam_lds_opt_in((const void*)k_dwt1_ana<LL, NN>, kLds1Cap)) return rc;                           \
-  hipLaunchKernelGGL((k_dwt1_ana<LL, NN>), dim3((unsigned)nb_blocks), dim3(kT1), lds, st, in, coeffs, filt, g, \
-                     t_lo, t_hi, NZ);
-#define WAM_D1A(LL)                                                                                          \
-  case LL:                                                                                                   \
-    if (nz) {                                                                                                \
-      WAM_D1AN(LL, true)                                                                                     \
-    } else {                                                                                                 \
-      WAM_D1AN(LL, false)                                                                                    \
-    }                                                                                                        \
-    break;
-      WAM_D1A(2) WAM_D1A(4) WAM_D1A(6) WAM_D1A(8) WAM_D1A(10) WAM_D1A(12) WAM_D1A(14) WAM_D1A(16) WAM_D1A(18)
-      WAM_D1A(20)
-#undef WAM_D1A
-#undef WAM_D1AN
-      default: return WAM_ERR_UNSUPPORTED;
-    }
+    if (int rc = dispatch_ln(p->L, nz != nullptr, [&](auto l, auto noise) -> int {
+          auto kern = k_dwt1_ana<decltype(l)::value, decltype(noise)::value>;
+          if (int rc = wam_lds_opt_in((const void*)kern, kLds1Cap)) return rc;
+          hipLaunchKernelGGL(kern, dim3((unsigned)nb_blocks), dim3(kT1), lds, st, in, coeffs, filt, g, t_lo, t_hi, NZ);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   }
   return WAM_OK;
@@ -1232,36 +1197,25 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
   // every tile on the persistent kernel (J <= 8; coefficient ranges are only ever clamped at the
   // right end, which its zero rule covers), k_dwt1_syn otherwise
   int t_lo = 0, t_hi = 0;
-  if (g.J <= 8 && syn_int_fits(p->L, g.J)) t_hi = g.tiles;
+  if (syn_int_fits(p->L, g.J)) t_hi = g.tiles;
   const int64_t units = batch * (int64_t)(t_hi - t_lo);
   int cus = 256;
-  if (units > 0) {
-    int dev = 0;
-    WAM_HIP_CHECK(hipGetDevice(&dev));
-    WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  if (units > 0) WAM_HIP_CHECK(wam_device_cus(&cus));
   const double bytes_all = 4.0 * ((double)batch * p->band_off[p->nbands] + (double)batch * (double)nout);
   for (int ai = 0; ai < n_alpha && units > 0; ++ai) {
     const float sc = alpha ? alpha[ai] : 1.0f;
     float* o = out + (int64_t)ai * batch * nout;
     const int64_t grid = std::min<int64_t>(units, 2LL * cus);
     WamTimer tm(st, "k_dwt1_syn_int", bytes_all * (double)(t_hi - t_lo) / g.tiles);
-    int rc = WAM_ERR_UNSUPPORTED;
-#define WAM_D1SI(LL, JJ)                                                                                        \
-  if (p->L == LL && g.J == JJ) {                                                                                \
-    using Sh = SynShape<LL, JJ>;                                                                                \
-    if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_int<LL, JJ>, kLds1Cap)) return e;                        \
-    hipLaunchKernelGGL((k_dwt1_syn_int<LL, JJ>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs, o, \
-                       filt, g, nout, sc, t_lo, t_hi, units);                                                  \
-    rc = WAM_OK;                                                                                                \
-  }
-#define WAM_D1SJ(LL) WAM_D1SI(LL, 1) WAM_D1SI(LL, 2) WAM_D1SI(LL, 3) WAM_D1SI(LL, 4) WAM_D1SI(LL, 5) \
-                     WAM_D1SI(LL, 6) WAM_D1SI(LL, 7) WAM_D1SI(LL, 8)
-    WAM_D1SJ(2) WAM_D1SJ(4) WAM_D1SJ(6) WAM_D1SJ(8) WAM_D1SJ(10) WAM_D1SJ(12) WAM_D1SJ(14) WAM_D1SJ(16)
-    WAM_D1SJ(18) WAM_D1SJ(20)
-#undef WAM_D1SJ
-#undef WAM_D1SI
-    if (rc) return rc;
+    if (int rc = wam_dispatch_len_levels(WamLensEven20{}, p->L, g.J, [&](auto l, auto j) -> int {
+          constexpr int L = decltype(l)::value, J = decltype(j)::value;
+          using Sh = SynShape<L, J>;
+          if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_int<L, J>, kLds1Cap)) return e;
+          hipLaunchKernelGGL((k_dwt1_syn_int<L, J>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs, o, filt,
+                             g, nout, sc, t_lo, t_hi, units);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   }
   const int64_t nb_blocks = batch * (int64_t)(g.tiles - (t_hi - t_lo));
@@ -1270,18 +1224,14 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
     const float sc = alpha ? alpha[ai] : 1.0f;
     float* o = out + (int64_t)ai * batch * nout;
     WamTimer tm(st, "k_dwt1_syn", bytes_all * (double)(g.tiles - (t_hi - t_lo)) / g.tiles);
-    switch (p->L) {
-#define WAM_D1S(LL)                                                                                            \
-  case LL:                                                                                                     \
-    if (int rc = wam_lds_opt_in((const void*)k_dwt1_syn<LL>, kLds1Cap)) return rc;                                   \
-    hipLaunchKernelGGL(k_dwt1_syn<LL>, dim3((unsigned)nb_blocks), dim3(kT1S), lds, st, coeffs, o, filt, g, nout, sc, \
-                       t_lo, t_hi);                                                                            \
-    break;
-      WAM_D1S(2) WAM_D1S(4) WAM_D1S(6) WAM_D1S(8) WAM_D1S(10) WAM_D1S(12) WAM_D1S(14) WAM_D1S(16) WAM_D1S(18)
-      WAM_D1S(20)
-#undef WAM_D1S
-      default: return WAM_ERR_UNSUPPORTED;
-    }
+    if (int rc = wam_dispatch_len(WamLensEven20{}, p->L, [&](auto l) -> int {
+          auto kern = k_dwt1_syn<decltype(l)::value>;
+          if (int rc = wam_lds_opt_in((const void*)kern, kLds1Cap)) return rc;
+          hipLaunchKernelGGL(kern, dim3((unsigned)nb_blocks), dim3(kT1S), lds, st, coeffs, o, filt, g, nout, sc, t_lo,
+                             t_hi);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   }
   return WAM_OK;
@@ -1292,7 +1242,7 @@ int launch_dwt1_tile_synthesis(const wam_plan* p, int64_t batch, const float* co
 // k_dwt1_syn_int on every tile. The ranked kernel keeps a rank beside every prefetched coefficient
 // (2 * nslots registers); every (L, J) k_dwt1_syn_int takes compiles without scratch.
 bool dwt1_syn_ranked_supported(const wam_plan* p) {
-  return p->ndim == 1 && p->routes.syn == WAM_WHOLE_TILE1 && p->levels <= 8 && syn_int_fits(p->L, p->levels);
+  return p->ndim == 1 && p->routes.syn == WAM_WHOLE_TILE1 && syn_int_fits(p->L, p->levels);
 }
 
 int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rtab,
@@ -1304,9 +1254,8 @@ int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const flo
   if (M > 65535 * 16 || rank_len > INT32_MAX) return WAM_ERR_INVALID_ARG;
   Dwt1Geom g = make_geom1(p, (int)p->lin[0][0], p->mode, sets);
   g.tiles = (nout + 2 * kTile0 - 1) / (2 * kTile0);
-  int dev = 0, cus = 256;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus = 256;
+  WAM_HIP_CHECK(wam_device_cus(&cus));
   // masks per unit: up to 16 (the mask expansion's chunk), fewer while the (set, tile, chunk) units
   // would not fill the persistent grid twice
   const int64_t st_units = sets * g.tiles;
@@ -1319,26 +1268,18 @@ int launch_dwt1_tile_synthesis_ranked(const wam_plan* p, int64_t sets, const flo
   const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;
   // algorithmic bytes: coefficients and ranks once per chunk, every reconstruction once
   WamTimer tm(st, "k_dwt1_syn_ranked", 4.0 * (2.0 * (double)sets * K * nchunks + (double)sets * M * nout));
-  int rc = WAM_ERR_UNSUPPORTED;
-#define WAM_D1SR(LL, JJ)                                                                                          \
-  if (p->L == LL && g.J == JJ) {                                                                                  \
-    using Sh = SynShape<LL, JJ>;                                                                                  \
-    if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_ranked<LL, JJ>, kLds1Cap)) return e;                       \
-    int wgs = 2;                                                                                                  \
-    WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_dwt1_syn_ranked<LL, JJ>, kT1,              \
-                                                               Sh::lds_bytes));                                   \
-    const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);                               \
-    hipLaunchKernelGGL((k_dwt1_syn_ranked<LL, JJ>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs,   \
-                       out, filt, g, nout, units, ra);                                                            \
-    rc = WAM_OK;                                                                                                  \
-  }
-#define WAM_D1SRJ(LL) WAM_D1SR(LL, 1) WAM_D1SR(LL, 2) WAM_D1SR(LL, 3) WAM_D1SR(LL, 4) WAM_D1SR(LL, 5) \
-                      WAM_D1SR(LL, 6) WAM_D1SR(LL, 7) WAM_D1SR(LL, 8)
-  WAM_D1SRJ(2) WAM_D1SRJ(4) WAM_D1SRJ(6) WAM_D1SRJ(8) WAM_D1SRJ(10) WAM_D1SRJ(12) WAM_D1SRJ(14) WAM_D1SRJ(16)
-  WAM_D1SRJ(18) WAM_D1SRJ(20)
-#undef WAM_D1SRJ
-#undef WAM_D1SR
-  if (rc) return rc;
+  if (int rc = wam_dispatch_len_levels(WamLensEven20{}, p->L, g.J, [&](auto l, auto j) -> int {
+        constexpr int L = decltype(l)::value, J = decltype(j)::value;
+        using Sh = SynShape<L, J>;
+        if (int e = wam_lds_opt_in((const void*)k_dwt1_syn_ranked<L, J>, kLds1Cap)) return e;
+        int wgs = 2;
+        WAM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_dwt1_syn_ranked<L, J>, kT1, Sh::lds_bytes));
+        const int64_t grid = std::min<int64_t>(units, (int64_t)std::max(1, wgs) * cus);
+        hipLaunchKernelGGL((k_dwt1_syn_ranked<L, J>), dim3((unsigned)grid), dim3(kT1), Sh::lds_bytes, st, coeffs, out,
+                           filt, g, nout, units, ra);
+        return WAM_OK;
+      }))
+    return rc;
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

@@ -18,6 +18,7 @@
 //
 // Waves are independent (no workgroup barriers): 4 waves per 256-thread block, LDS only for the
 // wave-private rows, ordered by the wave's own in-order LDS queue (wave-scope fences).
+#include "dispatch.hpp"
 #include "rowtools.hpp"
 
 namespace {
@@ -216,7 +217,7 @@ int launch_syn_L(int64_t batch, const float* H, const float* V, const float* D, 
 bool dwt2_fused_supported(const wam_plan* p) {
   // the streaming synthesis addresses a plane with 32-bit byte offsets (rowtools.hpp at32): a plane
   // of 2^30 floats or more would wrap, so such plans take the per-axis kernels
-  return p->ndim == 2 && p->L <= 20 && !(p->L & 1) && (p->shape[0] < (1 << 30)) && (p->shape[1] < (1 << 30)) &&
+  return p->ndim == 2 && wam_len_in(WamLensEven20{}, p->L) && (p->shape[0] < (1 << 30)) && (p->shape[1] < (1 << 30)) &&
          p->shape[0] * p->shape[1] < (int64_t(1) << 30) && p->rec_shape[0] * p->rec_shape[1] < (int64_t(1) << 30);
 }
 
@@ -227,14 +228,9 @@ int launch_dwt2_analysis_fused(const wam_plan* p, int64_t batch, const float* in
   int nh = (int)in_dims[0], nw = (int)in_dims[1], mh = (int)out_dims[0], mw = (int)out_dims[1];
   // sub order (ptwt): 0 = H ('da': hi along rows), 1 = V ('ad'), 2 = D
   float *oa = out_a, *oh = sub[0], *ov = sub[1], *od = sub[2];
-#define WAM_ANA_CASE(LL) \
-  case LL: return launch_ana_L<LL>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, p->pad, st);
-  switch (p->L) {
-    WAM_ANA_CASE(2) WAM_ANA_CASE(4) WAM_ANA_CASE(6) WAM_ANA_CASE(8) WAM_ANA_CASE(10)
-    WAM_ANA_CASE(12) WAM_ANA_CASE(14) WAM_ANA_CASE(16) WAM_ANA_CASE(18) WAM_ANA_CASE(20)
-    default: return WAM_ERR_UNSUPPORTED;
-  }
-#undef WAM_ANA_CASE
+  return wam_dispatch_len(WamLensEven20{}, p->L, [&](auto l) -> int {
+    return launch_ana_L<decltype(l)::value>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, p->pad, st);
+  });
 }
 
 int launch_dwt2_synthesis_fused(const wam_plan* p, int64_t batch, int level, const SynBatch& sb,
@@ -244,14 +240,9 @@ int launch_dwt2_synthesis_fused(const wam_plan* p, int64_t batch, int level, con
   int mh = (int)p->lout[level][0], mw = (int)p->lout[level][1];
   int nh = (int)(2 * mh - 2 + p->L - 2 * p->pad - p->extra[level][0]);
   int nw = (int)(2 * mw - 2 + p->L - 2 * p->pad - p->extra[level][1]);
-#define WAM_SYN_CASE(LL) \
-  case LL: return launch_syn_L<LL>(batch, sub[0], sub[1], sub[2], mh, mw, sb, nh, nw, p->pad, filt, st);
-  switch (p->L) {
-    WAM_SYN_CASE(2) WAM_SYN_CASE(4) WAM_SYN_CASE(6) WAM_SYN_CASE(8) WAM_SYN_CASE(10)
-    WAM_SYN_CASE(12) WAM_SYN_CASE(14) WAM_SYN_CASE(16) WAM_SYN_CASE(18) WAM_SYN_CASE(20)
-    default: return WAM_ERR_UNSUPPORTED;
-  }
-#undef WAM_SYN_CASE
+  return wam_dispatch_len(WamLensEven20{}, p->L, [&](auto l) -> int {
+    return launch_syn_L<decltype(l)::value>(batch, sub[0], sub[1], sub[2], mh, mw, sb, nh, nw, p->pad, filt, st);
+  });
 }
 
 // The same streaming level synthesis with a caller-chosen filter set (fset, fset + 1: lo then hi)
@@ -263,12 +254,7 @@ int launch_dwt2_synthesis_fused_to(const wam_plan* p, int64_t batch, int level, 
   const float* filt = p->d_filt + fset * p->L;
   int mh = (int)p->lout[level][0], mw = (int)p->lout[level][1];
   if (oh < 1 || ow < 1 || oh > 2 * mh - p->L + 2 || ow > 2 * mw - p->L + 2) return WAM_ERR_INVALID_ARG;
-#define WAM_SYN_CASE(LL) \
-  case LL: return launch_syn_L<LL>(batch, sub[0], sub[1], sub[2], mh, mw, sb, oh, ow, p->pad, filt, st);
-  switch (p->L) {
-    WAM_SYN_CASE(2) WAM_SYN_CASE(4) WAM_SYN_CASE(6) WAM_SYN_CASE(8) WAM_SYN_CASE(10)
-    WAM_SYN_CASE(12) WAM_SYN_CASE(14) WAM_SYN_CASE(16) WAM_SYN_CASE(18) WAM_SYN_CASE(20)
-    default: return WAM_ERR_UNSUPPORTED;
-  }
-#undef WAM_SYN_CASE
+  return wam_dispatch_len(WamLensEven20{}, p->L, [&](auto l) -> int {
+    return launch_syn_L<decltype(l)::value>(batch, sub[0], sub[1], sub[2], mh, mw, sb, oh, ow, p->pad, filt, st);
+  });
 }

@@ -24,6 +24,7 @@
 // XCD (L2); for noisy analysis the logical order is sample-fastest, so the S noise samples of one
 // clean plane run back to back on one XCD and its rows are read from HBM about once.
 
+#include "dispatch.hpp"
 #include "rowtools.hpp"
 
 namespace {
@@ -1016,9 +1017,9 @@ __global__ void __launch_bounds__(kPT) __attribute__((amdgpu_waves_per_eu(4, 8))
 }
 
 // ------------------------------------------------------------------------------------------------
-// filters up to 8 taps (haar, db2-db4, sym2-sym4, coif1): longer filters keep the per-level kernels,
-// whose register ring of L rows x 2 columns x lo/hi does not fit the 128-VGPR budget of 16 waves/CU
-bool l_ok(int L) { return L == 2 || L == 4 || L == 6 || L == 8; }
+// filters up to 8 taps (WamLensTo8: haar, db2-db4, sym2-sym4, coif1): longer filters keep the per-level
+// kernels, whose register ring of L rows x 2 columns x lo/hi does not fit the 128-VGPR budget of 16 waves/CU
+bool l_ok(int L) { return wam_len_in(WamLensTo8{}, L); }
 
 // cooperative level 1 (COOP): wave rows with 8 left pad slots + a ring of 2*8+L-2 (lo, hi) rows;
 // chosen when two workgroups still fit a CU (the ring replaces the wave-chunk halo re-fetch)
@@ -1132,21 +1133,15 @@ template <bool NOISE, int MC, bool MAPS>
 int dispatch_plane(const wam_plan* p, const PlaneGeom& g, int lds_bytes, int64_t n_items, const float* in,
                    float* out, float* band_max, const float* filt, const WamNoise& nz, int64_t S,
                    int64_t group_items, const char* name, double bytes, hipStream_t st) {
-  const bool two = g.mw[0] > 64;
-#define WAM_PLANE_ARGS g, lds_bytes, n_items, in, out, band_max, filt, nz, S, group_items, name, bytes, st
-#define WAM_PLANE_CASE(LL)                                                                                       \
-  case LL:                                                                                                       \
-    if (g.coop)                                                                                                  \
-      return two ? launch_plane_t<LL, 2, NOISE, MC, MAPS, true>(WAM_PLANE_ARGS)                                  \
-                 : launch_plane_t<LL, 1, NOISE, MC, MAPS, true>(WAM_PLANE_ARGS);                                 \
-    return two ? launch_plane_t<LL, 2, NOISE, MC, MAPS, false>(WAM_PLANE_ARGS)                                   \
-               : launch_plane_t<LL, 1, NOISE, MC, MAPS, false>(WAM_PLANE_ARGS);
-  switch (p->L) {
-    WAM_PLANE_CASE(2) WAM_PLANE_CASE(4) WAM_PLANE_CASE(6) WAM_PLANE_CASE(8)
-    default: return WAM_ERR_UNSUPPORTED;
-  }
-#undef WAM_PLANE_CASE
-#undef WAM_PLANE_ARGS
+  return wam_dispatch_len(WamLensTo8{}, p->L, [&](auto l) -> int {
+    return wam_dispatch_bool(g.coop, [&](auto coop) -> int {
+      return wam_dispatch_bool(g.mw[0] > 64, [&](auto two) -> int {  // two columns per lane
+        constexpr int L = decltype(l)::value, CPL = decltype(two)::value ? 2 : 1;
+        return launch_plane_t<L, CPL, NOISE, MC, MAPS, decltype(coop)::value>(
+            g, lds_bytes, n_items, in, out, band_max, filt, nz, S, group_items, name, bytes, st);
+      });
+    });
+  });
 }
 
 // the maps pass over bf16 input gradients (COOP level 1 only)
@@ -1155,19 +1150,14 @@ int dispatch_maps_bf16(const wam_plan* p, const PlaneGeom& g, int lds_bytes, int
                        float* out, float* band_max, const float* filt, int64_t group_items, double bytes,
                        hipStream_t st) {
   if (!g.coop) return WAM_ERR_UNSUPPORTED;
-  const bool two = g.mw[0] > 64;
   const char* name = IN == kInBf16Nhwc ? "k_plane_maps<bf16nhwc>" : "k_plane_maps<bf16>";
-#define WAM_MAPS_CASE(LL)                                                                                          \
-  case LL:                                                                                                         \
-    return two ? launch_plane_t<LL, 2, false, MC, true, true, IN>(g, lds_bytes, n_items, in, out, band_max, filt,  \
-                                                                   kNoNoise, 1, group_items, name, bytes, st)       \
-               : launch_plane_t<LL, 1, false, MC, true, true, IN>(g, lds_bytes, n_items, in, out, band_max, filt,  \
-                                                                   kNoNoise, 1, group_items, name, bytes, st);
-  switch (p->L) {
-    WAM_MAPS_CASE(2) WAM_MAPS_CASE(4) WAM_MAPS_CASE(6) WAM_MAPS_CASE(8)
-    default: return WAM_ERR_UNSUPPORTED;
-  }
-#undef WAM_MAPS_CASE
+  return wam_dispatch_len(WamLensTo8{}, p->L, [&](auto l) -> int {
+    return wam_dispatch_bool(g.mw[0] > 64, [&](auto two) -> int {  // two columns per lane
+      constexpr int L = decltype(l)::value, CPL = decltype(two)::value ? 2 : 1;
+      return launch_plane_t<L, CPL, false, MC, true, true, IN>(g, lds_bytes, n_items, in, out, band_max, filt, kNoNoise,
+                                                               1, group_items, name, bytes, st);
+    });
+  });
 }
 
 }  // namespace
@@ -1291,13 +1281,9 @@ int launch_syn_plane_t(const SynGeom& g, int lds_bytes, int64_t n_items, const f
 template <int OC>
 int syn_plane_l(int L, const SynGeom& g, int lds_bytes, int64_t n_items, const float* coeffs, void* out,
                 const float* filt, const SynAlphas& al, double bytes, hipStream_t st) {
-  switch (L) {
-    case 2: return launch_syn_plane_t<2, OC>(g, lds_bytes, n_items, coeffs, out, filt, al, bytes, st);
-    case 4: return launch_syn_plane_t<4, OC>(g, lds_bytes, n_items, coeffs, out, filt, al, bytes, st);
-    case 6: return launch_syn_plane_t<6, OC>(g, lds_bytes, n_items, coeffs, out, filt, al, bytes, st);
-    case 8: return launch_syn_plane_t<8, OC>(g, lds_bytes, n_items, coeffs, out, filt, al, bytes, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensTo8{}, L, [&](auto l) -> int {
+    return launch_syn_plane_t<decltype(l)::value, OC>(g, lds_bytes, n_items, coeffs, out, filt, al, bytes, st);
+  });
 }
 
 }  // namespace
@@ -1349,11 +1335,7 @@ int launch_dwt2_plane_synthesis_ranked(const wam_plan* p, int64_t images, int ch
   // algorithmic bytes: coefficients and ranks once, every reconstruction once
   const double bytes = 4.0 * ((double)planes * K + (double)images * K +
                               (double)planes * M * p->rec_shape[0] * p->rec_shape[1]);
-  switch (p->L) {
-    case 2: return launch_syn_ranked_t<2>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
-    case 4: return launch_syn_ranked_t<4>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
-    case 6: return launch_syn_ranked_t<6>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
-    case 8: return launch_syn_ranked_t<8>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensTo8{}, p->L, [&](auto l) -> int {
+    return launch_syn_ranked_t<decltype(l)::value>(g, lds_bytes, planes * M, coeffs, out, filt, ra, bytes, st);
+  });
 }

@@ -24,6 +24,7 @@
 // Waves are independent (no workgroup barriers). LDS writes and reads of a wave-private row are
 // ordered by the wave's in-order LDS queue; __builtin_amdgcn_wave_barrier() keeps the compiler
 // from reordering them.
+#include "dispatch.hpp"
 #include "rowtools.hpp"
 
 namespace {
@@ -589,12 +590,10 @@ int dispatch_adj(int channels, bool mean_first, int64_t images, const float* in,
   return WAM_ERR_UNSUPPORTED;
 }
 
-bool l_supported(int L) { return L == 2 || L == 4 || L == 6 || L == 8 || L == 12 || L == 16 || L == 20; }
-
 }  // namespace
 
 bool dwt2_rows_supported(const wam_plan* p, int level, bool adjoint) {
-  if (p->ndim != 2 || !l_supported(p->L)) return false;
+  if (p->ndim != 2 || !wam_len_in(WamLensRows{}, p->L)) return false;
   const int64_t nw = (adjoint && level == 0) ? p->rec_shape[1] : p->lin[level][1];
   return nw <= kMaxRow && nw >= 4;
 }
@@ -605,16 +604,9 @@ int launch_dwt2_analysis_rows(const wam_plan* p, int64_t batch, const float* in,
   const float* filt = p->d_filt + fset * p->L;
   const int nh = (int)in_dims[0], nw = (int)in_dims[1], mh = (int)out_dims[0], mw = (int)out_dims[1];
   float *oa = out_a, *oh = sub[0], *ov = sub[1], *od = sub[2];
-  switch (p->L) {
-    case 2: return dispatch_ana<2>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 4: return dispatch_ana<4>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 6: return dispatch_ana<6>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 8: return dispatch_ana<8>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 12: return dispatch_ana<12>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 16: return dispatch_ana<16>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    case 20: return dispatch_ana<20>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensRows{}, p->L, [&](auto l) -> int {
+    return dispatch_ana<decltype(l)::value>(batch, in, nh, nw, mh, mw, mode, filt, oa, oh, ov, od, nz, st);
+  });
 }
 
 int launch_dwt2_adjoint_maps_level(const wam_plan* p, int level, int64_t images, int channels, bool mean_first,
@@ -640,14 +632,7 @@ int launch_dwt2_adjoint_maps_level(const wam_plan* p, int level, int64_t images,
   ma.nbands = p->nbands;
   ma.group_items = group_items;
   ma.full_items = full_items;
-  switch (p->L) {
-    case 2: return dispatch_adj<2>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 4: return dispatch_adj<4>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 6: return dispatch_adj<6>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 8: return dispatch_adj<8>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 12: return dispatch_adj<12>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 16: return dispatch_adj<16>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    case 20: return dispatch_adj<20>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensRows{}, p->L, [&](auto l) -> int {
+    return dispatch_adj<decltype(l)::value>(channels, mean_first, images, in, nh, nw, mh, mw, filt, ll_out, ma, st);
+  });
 }

@@ -19,6 +19,7 @@
 // bit-identical to the generic path (tests/test_gpu_dwt.py). Longer filters keep the per-axis kernels:
 // their footprints leave too little of a tile in LDS to beat them (measured: sym8 2.4-8x slower in a
 // cubic-tile form, profiles/r06k_kbench_3d.log).
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -261,7 +262,7 @@ int launch_syn3(const Tile3Geom& g0, const Tile3Bands& b, float* out, const floa
 }
 
 bool tile3_ok(const wam_plan* p) {
-  if (p->ndim != 3 || p->L < 2 || p->L > 8 || (p->L & 1) || p->pad != p->L - 2) return false;
+  if (p->ndim != 3 || !wam_len_in(WamLensTo8{}, p->L) || p->pad != p->L - 2) return false;
   // 32-bit tile coordinates: every level's sizes stay below 2^30 when the reconstruction's do
   for (int a = 0; a < 3; ++a)
     if (p->rec_shape[a] >= (int64_t(1) << 30)) return false;
@@ -288,13 +289,9 @@ int launch_dwt3_analysis_tile(const wam_plan* p, int64_t batch, const float* in,
   b.b[0] = out_a;
   for (int key = 1; key < 8; ++key) b.b[key] = sub[key - 1];  // 3D: sub index = key - 1
   const float* filt = p->d_filt + fset * p->L;  // fset, fset + 1: lo then hi, adjacent
-  switch (p->L) {
-    case 2: return launch_ana3<2>(g, in, b, filt, st);
-    case 4: return launch_ana3<4>(g, in, b, filt, st);
-    case 6: return launch_ana3<6>(g, in, b, filt, st);
-    case 8: return launch_ana3<8>(g, in, b, filt, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensTo8{}, p->L, [&](auto l) -> int {
+    return launch_ana3<decltype(l)::value>(g, in, b, filt, st);
+  });
 }
 
 int launch_dwt3_synthesis_tile(const wam_plan* p, int64_t batch, int level, const float* a_in, float a_scale,
@@ -318,11 +315,7 @@ int launch_dwt3_synthesis_tile(const wam_plan* p, int64_t batch, int level, cons
     b.s[key] = d_scale;
   }
   const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;  // synthesis lo, then hi
-  switch (p->L) {
-    case 2: return launch_syn3<2>(g, b, out, filt, st);
-    case 4: return launch_syn3<4>(g, b, out, filt, st);
-    case 6: return launch_syn3<6>(g, b, out, filt, st);
-    case 8: return launch_syn3<8>(g, b, out, filt, st);
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  return wam_dispatch_len(WamLensTo8{}, p->L, [&](auto l) -> int {
+    return launch_syn3<decltype(l)::value>(g, b, out, filt, st);
+  });
 }

@@ -20,6 +20,7 @@
 //           preimage in a tail (strips about p wide along the four edges), the tail terms gathered
 //           straight from the four band planes. Needs n > p on both axes (the strips then hold every
 //           folded index); skipped in zero mode, where nothing folds.
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -328,17 +329,12 @@ int launch_dwt2_adjoint_fold(const wam_plan* p, int64_t batch, int level, const 
     const double strip = rows ? (double)nbr * nw : (double)nh * nbc;
     WamTimer tm(st, "k_dwt2_adjoint_border", 4.0 * 2.5 * (double)batch * strip);
     const dim3 grid((unsigned)(rows ? row_groups : col_groups));
-#define WAM_BORDER_CASE(LL)                                                                                         \
-  case LL:                                                                                                          \
-    hipLaunchKernelGGL(k_dwt2_adjoint_border<LL>, grid, dim3(256), 0, st, a, sub[0], sub[1], sub[2], mh, mw, out, nh, \
-                       nw, p->mode, filt, nbr, nbc, wl, wr, nchc, ngr, nchr, rows);                                 \
-    break;
-    switch (p->L) {
-      WAM_BORDER_CASE(2) WAM_BORDER_CASE(4) WAM_BORDER_CASE(6) WAM_BORDER_CASE(8) WAM_BORDER_CASE(10)
-      WAM_BORDER_CASE(12) WAM_BORDER_CASE(14) WAM_BORDER_CASE(16) WAM_BORDER_CASE(18) WAM_BORDER_CASE(20)
-      default: return WAM_ERR_UNSUPPORTED;
-    }
-#undef WAM_BORDER_CASE
+    if (int rc = wam_dispatch_len(WamLensEven20{}, p->L, [&](auto l) -> int {
+          hipLaunchKernelGGL(k_dwt2_adjoint_border<decltype(l)::value>, grid, dim3(256), 0, st, a, sub[0], sub[1],
+                             sub[2], mh, mw, out, nh, nw, p->mode, filt, nbr, nbc, wl, wr, nchc, ngr, nchr, rows);
+          return WAM_OK;
+        }))
+      return rc;
     WAM_LAUNCH_CHECK();
   }
   return WAM_OK;

@@ -21,11 +21,14 @@
 // index  (device, int32): band_ptr[n_mels+1] | band_bin[nnz] | bin_ptr[N/2+2] | bin_band[nnz]
 // (the filterbank's nonzeros by band and by bin, built on the host from torchaudio's HTK
 // filterbank: wam_amd/melspec.py).
+#include "dispatch.hpp"
 #include "kernels.hpp"
 
 #include <algorithm>
 
 namespace {
+
+using MelLogN = WamLens<6, 7, 8, 9, 10, 11>;  // log2 of the FFT sizes with a kernel instantiation
 
 constexpr int kWavesF = 4;  // forward: waves per workgroup, each streaming frames (one frame per wave at a time)
 
@@ -706,26 +709,18 @@ extern "C" int wam_melspec(int64_t items, int64_t samples, int n_fft, int n_mels
   const int lds = lds_fwd(log_n, n_mels, nnz);
   if (lds > kMaxLds) return WAM_ERR_UNSUPPORTED;
   int cus = 256;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
+  (void)wam_device_cus(&cus);  // a failed query leaves 256
   // persistent-ish grid: a few workgroups per CU, each wave streaming frames with one-ahead prefetch
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((frames + kWavesF - 1) / kWavesF, 4 * cus));
   WamTimer tm(st, "k_mel_fwd", 4.0 * (double)items * samples + 4.0 * (double)frames * n_mels);
-  switch (log_n) {
-#define WAM_MELF(L)                                                                                           \
-  case L:                                                                                                     \
-    if (int rc = wam_lds_opt_in((const void*)k_mel_fwd<L, (L <= 10)>, kMaxLds)) return rc;                    \
-    hipLaunchKernelGGL((k_mel_fwd<L, (L <= 10)>), dim3(grid), dim3(64 * kWavesF), lds, st, g, wave, tables, index, \
-                       out);                                                                                  \
-    break;
-    WAM_MELF(6) WAM_MELF(7) WAM_MELF(8) WAM_MELF(9) WAM_MELF(10) WAM_MELF(11)
-#undef WAM_MELF
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  if (int rc = wam_dispatch_len(MelLogN{}, log_n, [&](auto ln) -> int {
+        constexpr int L = decltype(ln)::value;
+        if (int rc = wam_lds_opt_in((const void*)k_mel_fwd<L, (L <= 10)>, kMaxLds)) return rc;
+        hipLaunchKernelGGL((k_mel_fwd<L, (L <= 10)>), dim3(grid), dim3(64 * kWavesF), lds, st, g, wave, tables, index,
+                           out);
+        return WAM_OK;
+      }))
+    return rc;
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -752,21 +747,17 @@ extern "C" int wam_melspec_adjoint(int64_t items, int64_t samples, int n_fft, in
   if (lds > kMaxLds) return WAM_ERR_UNSUPPORTED;
   const void* kern = nullptr;
   const void* kfold = nullptr;
-  switch (log_n) {
-#define WAM_MELR(L)                                     \
-  case L:                                               \
-    kern = (const void*)k_mel_adj_run<L, (L <= 10)>;    \
-    kfold = (const void*)k_mel_fold<L, (L <= 10)>;      \
-    break;
-    WAM_MELR(6) WAM_MELR(7) WAM_MELR(8) WAM_MELR(9) WAM_MELR(10) WAM_MELR(11)
-#undef WAM_MELR
-    default: return WAM_ERR_UNSUPPORTED;
-  }
+  if (int rc = wam_dispatch_len(MelLogN{}, log_n, [&](auto ln) -> int {
+        constexpr int L = decltype(ln)::value;
+        kern = (const void*)k_mel_adj_run<L, (L <= 10)>;
+        kfold = (const void*)k_mel_fold<L, (L <= 10)>;
+        return WAM_OK;
+      }))
+    return rc;
   if (int rc = wam_lds_opt_in(kern, kMaxLds)) return rc;
   if (int rc = wam_lds_opt_in(kfold, kMaxLds)) return rc;
-  int dev = 0, cus = 256, per_cu = 1;
-  WAM_HIP_CHECK(hipGetDevice(&dev));
-  WAM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus = 256, per_cu = 1;
+  WAM_HIP_CHECK(wam_device_cus(&cus));
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kWavesR, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
   // runs of about 16 hop-blocks (one extra frame each), their count rounded to whole rounds of the
@@ -780,28 +771,22 @@ extern "C" int wam_melspec_adjoint(int64_t items, int64_t samples, int n_fft, in
   const unsigned fold_wgs = (unsigned)((2 * items + kWavesR - 1) / kWavesR);
   {
     WamTimer tm(st, "k_mel_adj", 8.0 * (double)items * samples + 4.0 * (double)items * g.F * n_mels);
-    switch (log_n) {
-#define WAM_MELR(L)                                                                                       \
-  case L:                                                                                                 \
-    hipLaunchKernelGGL((k_mel_adj_run<L, (L <= 10)>), dim3((unsigned)wgs), dim3(64 * kWavesR), lds, st, g, rg, \
-                       wave, grad_out, tables, index, grad_wave);                                         \
-    break;
-      WAM_MELR(6) WAM_MELR(7) WAM_MELR(8) WAM_MELR(9) WAM_MELR(10) WAM_MELR(11)
-#undef WAM_MELR
-    }
+    wam_dispatch_len(MelLogN{}, log_n, [&](auto ln) -> int {
+      constexpr int L = decltype(ln)::value;
+      hipLaunchKernelGGL((k_mel_adj_run<L, (L <= 10)>), dim3((unsigned)wgs), dim3(64 * kWavesR), lds, st, g, rg, wave,
+                         grad_out, tables, index, grad_wave);
+      return WAM_OK;
+    });
     WAM_LAUNCH_CHECK();
   }
   // the folds: two frames per waveform recomputed, 2 hop samples read and written
   WamTimer tm(st, "k_mel_fold", 4.0 * (double)items * (2.0 * n_fft + 2.0 * n_mels + 4.0 * g.hop));
-  switch (log_n) {
-#define WAM_MELR(L)                                                                                            \
-  case L:                                                                                                      \
-    hipLaunchKernelGGL((k_mel_fold<L, (L <= 10)>), dim3(fold_wgs), dim3(64 * kWavesR), lds, st, g, wave, grad_out, \
-                       tables, index, grad_wave);                                                              \
-    break;
-    WAM_MELR(6) WAM_MELR(7) WAM_MELR(8) WAM_MELR(9) WAM_MELR(10) WAM_MELR(11)
-#undef WAM_MELR
-  }
+  wam_dispatch_len(MelLogN{}, log_n, [&](auto ln) -> int {
+    constexpr int L = decltype(ln)::value;
+    hipLaunchKernelGGL((k_mel_fold<L, (L <= 10)>), dim3(fold_wgs), dim3(64 * kWavesR), lds, st, g, wave, grad_out, tables,
+                       index, grad_wave);
+    return WAM_OK;
+  });
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

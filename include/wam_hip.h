@@ -754,6 +754,23 @@ int wam_ew_add_bias_relu(int dtype, int64_t n, int64_t channels, int64_t inner, 
 /* out = y > 0 ? g1 (+ g2 if g2 != NULL) : 0          (ReLU backward, optionally fused fan-in) */
 int wam_ew_relu_mask(int dtype, int64_t n, const void* g1, const void* g2, const void* y, void* out,
                      void* stream);
+/* Packed ReLU masks. mask: uint8 [n / 8], bit i % 8 of byte i / 8 is out[i] > 0 on the stored bf16
+ * value (0 for +0, -0, negatives and NaN; 1 for denormals and +inf), i the flat element index in
+ * whatever layout the tensor has. The two producers store exactly what wam_ew_bias_act (relu != 0) /
+ * wam_ew_add_bias_relu store and write the mask of it as well; the consumer is wam_ew_relu_mask with
+ * the bit in place of y > 0, so fed a producer's mask it returns what wam_ew_relu_mask fed that
+ * producer's output returns, at 1/16 of the y bytes. WAM_DT_BF16 only, n % 8 == 0, every pointer
+ * (mask included) 16-byte aligned, and for the producers a channel layout with whole 16-byte vectors
+ * (inner == 1 and channels % 8 == 0, or inner % 8 == 0): anything else is WAM_ERR_UNSUPPORTED with
+ * nothing written (run the plain entry instead). A NULL mask is WAM_ERR_INVALID_ARG. */
+int wam_ew_bias_act_bits(int dtype, int64_t n, int64_t channels, int64_t inner, void* y, const void* bias,
+                         void* mask, void* stream);
+int wam_ew_add_bias_relu_bits(int dtype, int64_t n, int64_t channels, int64_t inner, const void* a,
+                              const void* bias_a, const void* s, const void* bias_s, void* out, void* mask,
+                              void* stream);
+/* out = bit ? g1 (+ g2 if g2 != NULL) : 0 */
+int wam_ew_relu_mask_bits(int dtype, int64_t n, const void* g1, const void* g2, const void* mask, void* out,
+                          void* stream);
 /* NHWC max pooling (k x k window, stride, zero-area padding pad <= k/2, floor output size):
  * y [n, ho, wo, c], idx [n, ho, wo, c] uint8 = window position kh*k+kw | 0x80 if the max is > 0.
  * Scan order kh*k+kw over the positions inside the image, as torch: the first of equal maxima wins,
@@ -763,6 +780,12 @@ int wam_ew_relu_mask(int dtype, int64_t n, const void* g1, const void* g2, const
  * WAM_ERR_UNSUPPORTED when c is not a multiple of the 16-byte vector or pointers are unaligned. */
 int wam_ew_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride, int pad,
                         const void* x, void* y, void* idx, void* stream);
+/* wam_ew_maxpool_nhwc of relu(x + bias[c]) as wam_ew_bias_act (relu form, NHWC) stores it, taken on
+ * each element as it is loaded: y and idx are what that call on x followed by the pool give, x is left
+ * as it is and the biased tensor is never written. bias: c values, not NULL (WAM_ERR_INVALID_ARG),
+ * 16-byte aligned (WAM_ERR_UNSUPPORTED otherwise, as for the other pointers). */
+int wam_ew_bias_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride, int pad,
+                             const void* x, const void* bias, void* y, void* idx, void* stream);
 /* gx [n, h, w, c] = sum of gy over the windows whose idx points at the pixel (fp32 sums in window
  * order); relu != 0 also drops windows whose max was not > 0 (mask of the ReLU feeding the pool). */
 int wam_ew_maxpool_nhwc_backward(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride,
@@ -779,13 +802,18 @@ int wam_ew_maxpool_nhwc_backward(int dtype, int64_t n, int64_t h, int64_t w, int
  * mode | WAM_PW_ROUNDED: acc is rounded to bf16 (nearest even) before the epilogue, i.e. the epilogue
  * sees the value a bf16 GEMM followed by wam_ew_add_bias_relu / wam_ew_relu_mask sees; results then
  * equal that pair's wherever the two fp32 accumulation orders round to the same bf16 value.
+ * mode | WAM_PW_BITS: r1 is the packed ReLU mask of [M, N] (uint8 [M N / 8], the format of
+ * wam_ew_add_bias_relu_bits; 16-byte aligned like the other operands). WAM_PW_TAIL writes it there,
+ * from the values it stores in out (r1 must then not be NULL; it is written although the parameter
+ * is declared const); WAM_PW_MASK reads it in place of y, bit set = y > 0. out is what the unflagged
+ * launch gives, bit for bit; rows past M of a ragged tile write no mask byte.
  * wam_pw_supported: 1 for bf16 with (K, N) = (64, 256) or (128, 512), else 0. wam_pw_gemm returns
  * WAM_ERR_UNSUPPORTED (out untouched) for another dtype or (K, N) or when x, w, r0, r1 or out is not
  * 16-byte aligned, WAM_ERR_INVALID_ARG for M <= 0, a NULL x / w / out, an unknown mode or dtype, or
  * operands the mode does not take. out must not alias an input. wam_pw_gemm_ex caps the persistent
  * grid at max_workgroups per N split (0: the resident count), so that a test can make every
  * workgroup loop over several tiles of a small M. */
-enum wam_pw_mode { WAM_PW_TAIL = 0, WAM_PW_MASK = 1, WAM_PW_ROUNDED = 16 };
+enum wam_pw_mode { WAM_PW_TAIL = 0, WAM_PW_MASK = 1, WAM_PW_ROUNDED = 16, WAM_PW_BITS = 32 };
 int wam_pw_supported(int dtype, int64_t K, int64_t N);
 int wam_pw_gemm(int mode, int dtype, int64_t M, int64_t K, int64_t N, const void* x, const void* w,
                 const void* bias_a, const void* bias_b, const void* r0, const void* r1, void* out, void* stream);

@@ -8,7 +8,10 @@ group shapes (batch 832, bf16): M = 832 * 56^2 for (K, N) = (64, 256), M = 832 *
 HIP events around every launch (pair), `--iters` launches after warm-up; the median is reported,
 with GB/s on the fused launch's algorithmic bytes (X + s|y,g2 + out + W).
 
-usage: python scripts/kbench_pointwise.py [--iters 20] [--batch 832]
+--relubits times the packed-mask forms instead (wam_ew_*_bits, wam_pw_gemm | WAM_PW_BITS, the junction
+sum and wam_ew_bias_maxpool_nhwc), each against the launches it replaces: see relubits().
+
+usage: python scripts/kbench_pointwise.py [--iters 20] [--batch 832] [--relubits]
 """
 import argparse
 import os
@@ -37,12 +40,85 @@ def timed(fn, iters):
     return t[len(t) // 2] * 1e3, t[0] * 1e3  # median, min in us
 
 
+def relubits(args):
+    """The packed-mask forms, the junction sum and the stem pool against the launches they replace, at
+    the c2 activation sizes: [832 * 56^2, 256] (block outputs of stage 2), [832 * 56^2, 64] (its conv2
+    outputs) and the stem's [832, 112, 112, 64] convolution output."""
+    bf = torch.bfloat16
+    st = lambda: _lib.stream_of(torch.device("cuda"))  # noqa: E731
+    p, L, ck = _lib.ptr, _lib.lib, _lib.check
+    print("%-22s %12s | %9s | %9s %9s | %s" % ("form", "elements", "today us", "new us", "min us", "new / today"))
+
+    def row(name, n, today, new):
+        t0, _ = timed(today, args.iters)
+        t1, t1min = timed(new, args.iters)
+        print("%-22s %12d | %9.1f | %9.1f %9.1f | %.3f" % (name, n, t0, t1, t1min, t1 / t0), flush=True)
+
+    for C in (256, 64):
+        n = args.batch * 56 * 56 * C
+        g1, g2 = torch.randn(n, device="cuda").to(bf), torch.randn(n, device="cuda").to(bf)
+        a, s = torch.randn(n, device="cuda").to(bf), torch.randn(n, device="cuda").to(bf)
+        b = torch.randn(C, device="cuda").to(bf)
+        y = torch.relu(torch.randn(n, device="cuda")).to(bf)
+        out, tmp = torch.empty_like(y), torch.empty_like(y)
+        m = torch.empty(n // 8, dtype=torch.uint8, device="cuda")
+        ck(L.wam_ew_add_bias_relu_bits(1, n, C, 1, p(a), p(b), p(s), p(b), p(y), p(m), st()))
+        row("mask C=%d" % C, n, lambda: ck(L.wam_ew_relu_mask(1, n, p(g1), None, p(y), p(out), st())),
+            lambda: ck(L.wam_ew_relu_mask_bits(1, n, p(g1), None, p(m), p(out), st())))
+        row("mask + g2 C=%d" % C, n, lambda: ck(L.wam_ew_relu_mask(1, n, p(g1), p(g2), p(y), p(out), st())),
+            lambda: ck(L.wam_ew_relu_mask_bits(1, n, p(g1), p(g2), p(m), p(out), st())))
+        row("junction C=%d" % C, n,
+            lambda: (torch.add(g1, g2, out=tmp), ck(L.wam_ew_relu_mask(1, n, p(tmp), None, p(y), p(out), st()))),
+            lambda: ck(L.wam_ew_relu_mask_bits(1, n, p(g1), p(g2), p(m), p(out), st())))
+        row("junction, y C=%d" % C, n,
+            lambda: (torch.add(g1, g2, out=tmp), ck(L.wam_ew_relu_mask(1, n, p(tmp), None, p(y), p(out), st()))),
+            lambda: ck(L.wam_ew_relu_mask(1, n, p(g1), p(g2), p(y), p(out), st())))
+        row("add_bias_relu+bits C=%d" % C, n,
+            lambda: ck(L.wam_ew_add_bias_relu(1, n, C, 1, p(a), p(b), p(s), p(b), p(out), st())),
+            lambda: ck(L.wam_ew_add_bias_relu_bits(1, n, C, 1, p(a), p(b), p(s), p(b), p(out), p(m), st())))
+        row("bias_act+bits C=%d" % C, n, lambda: ck(L.wam_ew_bias_act(1, n, C, 1, p(tmp), p(b), 1, st())),
+            lambda: ck(L.wam_ew_bias_act_bits(1, n, C, 1, p(tmp), p(b), p(m), st())))
+        del g1, g2, a, s, y, out, tmp, m
+    # wam_pw_gemm with the packed mask: TAIL writing it, MASK (with g2, as the model launches it) reading it
+    BITS = 32
+    for K, N, hw in ((64, 256, 56), (128, 512, 28)):
+        M = args.batch * hw * hw
+        x = torch.randn(M, K, device="cuda").to(bf)
+        w = (torch.randn(N, K, device="cuda") / K ** 0.5).to(bf)
+        ba, bs = torch.randn(N, device="cuda").to(bf), torch.randn(N, device="cuda").to(bf)
+        s = torch.randn(M, N, device="cuda").to(bf)
+        y = torch.relu(torch.randn(M, N, device="cuda")).to(bf)
+        out = torch.empty(M, N, device="cuda", dtype=bf)
+        m = torch.empty(M * N // 8, dtype=torch.uint8, device="cuda")
+        row("pw tail+bits %dx%d" % (K, N), M * N,
+            lambda: ck(L.wam_pw_gemm(0 | ROUNDED, 1, M, K, N, p(x), p(w), p(ba), p(bs), p(s), None, p(out), st())),
+            lambda: ck(L.wam_pw_gemm(0 | ROUNDED | BITS, 1, M, K, N, p(x), p(w), p(ba), p(bs), p(s), p(m), p(out), st())))
+        ck(L.wam_ew_add_bias_relu_bits(1, M * N, N, 1, p(s), None, p(s), None, p(y), p(m), st()))
+        row("pw mask, bits %dx%d" % (K, N), M * N,
+            lambda: ck(L.wam_pw_gemm(1 | ROUNDED, 1, M, K, N, p(x), p(w), None, None, p(s), p(y), p(out), st())),
+            lambda: ck(L.wam_pw_gemm(1 | ROUNDED | BITS, 1, M, K, N, p(x), p(w), None, None, p(s), p(m), p(out), st())))
+        del x, s, y, out, m
+    N, H, C = args.batch, 112, 64
+    x = torch.randn(N * H * H * C, device="cuda").to(bf)
+    t = x.clone()
+    b = torch.randn(C, device="cuda").to(bf)
+    yo = torch.empty(N * 56 * 56 * C, device="cuda", dtype=bf)
+    idx = torch.empty(N * 56 * 56 * C, device="cuda", dtype=torch.uint8)
+    row("stem bias+relu+pool", x.numel(),
+        lambda: (ck(L.wam_ew_bias_act(1, t.numel(), C, 1, p(t), p(b), 1, st())),
+                 ck(L.wam_ew_maxpool_nhwc(1, N, H, H, C, 3, 2, 1, p(t), p(yo), p(idx), st()))),
+        lambda: ck(L.wam_ew_bias_maxpool_nhwc(1, N, H, H, C, 3, 2, 1, p(x), p(b), p(yo), p(idx), st())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=832)
+    ap.add_argument("--relubits", action="store_true", help="the packed-mask, junction and stem-pool pairs only")
     args = ap.parse_args()
     torch.manual_seed(0)
+    if args.relubits:
+        return relubits(args)
     bf = torch.bfloat16
     st = lambda: _lib.stream_of(torch.device("cuda"))  # noqa: E731
     print("%-5s %-9s %10s | %9s %9s %9s | %9s %9s %7s | %s" % ("mode", "K x N", "M", "mm us", "ew us", "pair us",

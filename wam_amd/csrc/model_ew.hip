@@ -12,7 +12,11 @@
 //   k_relu_mask     out = y > 0 ? g : 0                        (ReLU backward)
 //   k_add_relu_mask out = y > 0 ? g1 + g2 : 0                  (gradient fan-in + ReLU backward)
 //   k_maxpool_fwd / k_maxpool_bwd  NHWC max pooling with a byte window index; the backward
-//                   also applies the mask of the ReLU that fed the pool (stem relu -> maxpool)
+//                   also applies the mask of the ReLU that fed the pool (stem relu -> maxpool);
+//                   the forward can apply the producer's bias + ReLU to each element it loads
+//   k_bias_act_bits / k_add_bias_relu_bits / k_relu_mask_bits  (bf16) the ReLU producers also write
+//                   one bit per element, out > 0, and the backward mask reads that bit in place of
+//                   the activation: 1/16 of its bytes (a thread's 16-byte vector is one mask byte)
 // Arithmetic in fp32, storage fp32 or bf16 (round to nearest even on the store). Every kernel
 // moves 16 bytes per access (8 bf16 / 4 fp32) with UNR accesses in flight per thread; the channel
 // of an element is (i / inner) % C (inner = 1 for NHWC, H*W for NCHW).
@@ -20,6 +24,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "relubits.hpp"
 
 namespace {
 
@@ -200,6 +205,107 @@ __global__ void __launch_bounds__(kBlk) k_relu_mask(int64_t nvec, const T* g1, c
   }
 }
 
+
+// k_bias_act<uint16_t, CH, true> that also writes the mask of what it stores
+template <int CH>
+__global__ void __launch_bounds__(kBlk) k_bias_act_bits(int64_t nvec, int64_t C, int64_t inner, uint16_t* __restrict__ y,
+                                                          const uint16_t* __restrict__ b, uint8_t* __restrict__ mask) {
+  typedef uint16_t T;
+  constexpr int V = Vec<T>::N;
+  typedef typename Vec<T>::raw R;
+  const int64_t base = (int64_t)blockIdx.x * (kBlk * kUnr) + threadIdx.x;
+  R r[kUnr];
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q < nvec) r[u] = reinterpret_cast<const R*>(y)[q];
+  }
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q >= nvec) continue;
+    float v[V], bv[V];
+    Vec<T>::unpack(r[u], v);
+    load_bias<T, CH>(b, q * V, C, inner, bv);
+#pragma unroll
+    for (int k = 0; k < V; ++k) v[k] += bv[k];
+    const R o = Vec<T>::pack_relu(v);
+    reinterpret_cast<R*>(y)[q] = o;
+    mask[q] = (uint8_t)wam_pos_bits(o);
+  }
+}
+
+// k_add_bias_relu<uint16_t, CH> that also writes the mask of what it stores
+template <int CH>
+__global__ void __launch_bounds__(kBlk) k_add_bias_relu_bits(int64_t nvec, int64_t C, int64_t inner, const uint16_t* a,
+                                                               const uint16_t* __restrict__ ba, const uint16_t* s,
+                                                               const uint16_t* __restrict__ bs, uint16_t* out,
+                                                               uint8_t* __restrict__ mask) {
+  typedef uint16_t T;
+  constexpr int V = Vec<T>::N;
+  typedef typename Vec<T>::raw R;
+  const int64_t base = (int64_t)blockIdx.x * (kBlk * kUnr) + threadIdx.x;
+  R ra[kUnr], rs[kUnr];
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q < nvec) {
+      ra[u] = reinterpret_cast<const R*>(a)[q];
+      rs[u] = reinterpret_cast<const R*>(s)[q];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q >= nvec) continue;
+    float va[V], vs[V], b1[V], b2[V];
+    Vec<T>::unpack(ra[u], va);
+    Vec<T>::unpack(rs[u], vs);
+    load_bias<T, CH>(ba, q * V, C, inner, b1);
+    load_bias<T, CH>(bs, q * V, C, inner, b2);
+#pragma unroll
+    for (int k = 0; k < V; ++k) va[k] = (va[k] + b1[k]) + (vs[k] + b2[k]);
+    const R o = Vec<T>::pack_relu(va);
+    reinterpret_cast<R*>(out)[q] = o;
+    mask[q] = (uint8_t)wam_pos_bits(o);
+  }
+}
+
+// out = bit ? (g1 [+ g2]) : 0 -- k_relu_mask<uint16_t, TWO> with the mask byte in place of y's vector
+template <bool TWO>
+__global__ void __launch_bounds__(kBlk) k_relu_mask_bits(int64_t nvec, const uint16_t* g1, const uint16_t* g2,
+                                                           const uint8_t* __restrict__ mask, uint16_t* out) {
+  typedef uint16_t T;
+  constexpr int V = Vec<T>::N;
+  typedef typename Vec<T>::raw R;
+  const int64_t base = (int64_t)blockIdx.x * (kBlk * kUnr) + threadIdx.x;
+  R rg[kUnr], rh[kUnr];
+  uint32_t rm[kUnr];
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q < nvec) {
+      rg[u] = reinterpret_cast<const R*>(g1)[q];
+      if (TWO) rh[u] = reinterpret_cast<const R*>(g2)[q];
+      rm[u] = mask[q];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kUnr; ++u) {
+    const int64_t q = base + u * kBlk;
+    if (q >= nvec) continue;
+    float vg[V], vh[V];
+    Vec<T>::unpack(rg[u], vg);
+    if (TWO) Vec<T>::unpack(rh[u], vh);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const float gv = TWO ? vg[k] + vh[k] : vg[k];
+      vg[k] = (rm[u] >> k) & 1u ? gv : 0.f;
+    }
+    reinterpret_cast<R*>(out)[q] = Vec<T>::pack(vg);
+  }
+}
+
 // scalar fallbacks (unaligned pointers, ragged sizes, channel runs not a multiple of the vector)
 template <typename T>
 __global__ void __launch_bounds__(kBlk) k_ew_scalar(int op, int64_t n, int64_t C, int64_t inner, const T* a,
@@ -289,6 +395,52 @@ int relu_mask(int64_t n, const void* g1_, const void* g2_, const void* y_, void*
   return WAM_OK;
 }
 
+// the bits forms serve bf16, n % 8 == 0 and 16-byte aligned operands only; anything else is refused
+// before a launch (the caller then runs the plain entry)
+int bias_act_bits(int64_t n, int64_t C, int64_t inner, void* y_, const void* b_, void* mask, hipStream_t st) {
+  typedef uint16_t T;
+  T* y = (T*)y_;
+  const T* b = (const T*)b_;
+  if (!al16(mask)) return WAM_ERR_UNSUPPORTED;
+  const int lay = channel_layout<T>(n, C, inner, {y}, {b});
+  const int64_t nv = n / Vec<T>::N;
+  if (lay == CH_VEC) hipLaunchKernelGGL((k_bias_act_bits<CH_VEC>), vec_grid(nv), kBlk, 0, st, nv, C, inner, y, b, (uint8_t*)mask);
+  else if (lay == CH_ONE) hipLaunchKernelGGL((k_bias_act_bits<CH_ONE>), vec_grid(nv), kBlk, 0, st, nv, C, inner, y, b, (uint8_t*)mask);
+  else return WAM_ERR_UNSUPPORTED;
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int add_bias_relu_bits(int64_t n, int64_t C, int64_t inner, const void* a_, const void* ba_, const void* s_,
+                       const void* bs_, void* out_, void* mask, hipStream_t st) {
+  typedef uint16_t T;
+  const T *a = (const T*)a_, *ba = (const T*)ba_, *s = (const T*)s_, *bs = (const T*)bs_;
+  T* out = (T*)out_;
+  if (!al16(mask)) return WAM_ERR_UNSUPPORTED;
+  const int lay = channel_layout<T>(n, C, inner, {a, s, out}, {ba, bs});
+  const int64_t nv = n / Vec<T>::N;
+  if (lay == CH_VEC)
+    hipLaunchKernelGGL((k_add_bias_relu_bits<CH_VEC>), vec_grid(nv), kBlk, 0, st, nv, C, inner, a, ba, s, bs, out, (uint8_t*)mask);
+  else if (lay == CH_ONE)
+    hipLaunchKernelGGL((k_add_bias_relu_bits<CH_ONE>), vec_grid(nv), kBlk, 0, st, nv, C, inner, a, ba, s, bs, out, (uint8_t*)mask);
+  else
+    return WAM_ERR_UNSUPPORTED;
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int relu_mask_bits(int64_t n, const void* g1, const void* g2, const void* mask, void* out, hipStream_t st) {
+  typedef uint16_t T;
+  if (n % Vec<T>::N || !al16(g1) || (g2 && !al16(g2)) || !al16(mask) || !al16(out)) return WAM_ERR_UNSUPPORTED;
+  const int64_t nv = n / Vec<T>::N;
+  if (g2)
+    hipLaunchKernelGGL((k_relu_mask_bits<true>), vec_grid(nv), kBlk, 0, st, nv, (const T*)g1, (const T*)g2, (const uint8_t*)mask, (T*)out);
+  else
+    hipLaunchKernelGGL((k_relu_mask_bits<false>), vec_grid(nv), kBlk, 0, st, nv, (const T*)g1, (const T*)g2, (const uint8_t*)mask, (T*)out);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
 
 // ---- max pooling over a channels_last (NHWC) activation, window index kept as one byte
 // Forward: one thread per (n, oy, ox, 16-byte channel vector); max in window scan order with
@@ -311,9 +463,17 @@ __device__ __forceinline__ int div_sh(int a, int sh, int d) { return sh >= 0 ? (
 // KC: compile-time window size (3 for the ResNet stem; 0 = runtime g.k). With KC all k*k loads
 // are issued at once from clamped addresses and masked afterwards, instead of a loop of dependent
 // load rounds (the kernel is latency-bound otherwise).
-template <typename T, int KC>
-__global__ void __launch_bounds__(kBlk) k_maxpool_fwd(PoolGeom g, const T* __restrict__ x, T* __restrict__ y,
-                                                        uint8_t* __restrict__ idx) {
+// the value k_bias_act<T, CH_VEC, true> stores for x + b, as the float the pool would load back
+__device__ __forceinline__ float stored_relu(float v, const float*) { return relu_f(v); }
+__device__ __forceinline__ float stored_relu(float v, const uint16_t*) {
+  return __uint_as_float((uint32_t)f2bf_relu(v) << 16);
+}
+
+// BIAS: the pooled tensor is relu(x + b[c]) as k_bias_act stores it, taken on each loaded element
+// (the stem's bias + ReLU pass and its 2 round trips over the convolution output are then not made)
+template <typename T, int KC, bool BIAS>
+__global__ void __launch_bounds__(kBlk) k_maxpool_fwd(PoolGeom g, const T* __restrict__ x, const T* __restrict__ bias,
+                                                        T* __restrict__ y, uint8_t* __restrict__ idx) {
   constexpr int V = Vec<T>::N;
   typedef typename Vec<T>::raw R;
   // grid (x: output column x channel vector, y: output row, z: image): no 64-bit divides, which
@@ -330,6 +490,14 @@ __global__ void __launch_bounds__(kBlk) k_maxpool_fwd(PoolGeom g, const T* __res
   int id[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) m[j] = -INFINITY, id[j] = ky0 * g.k + kx0;
+  float bv[V];
+  if constexpr (BIAS) Vec<T>::unpack(*reinterpret_cast<const R*>(bias + c0), bv);
+  auto act = [&](float (&v)[V]) {
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[j] = stored_relu(v[j] + bv[j], x);
+    }
+  };
   if constexpr (KC > 0) {
     R raw[KC * KC];
 #pragma unroll
@@ -348,6 +516,7 @@ __global__ void __launch_bounds__(kBlk) k_maxpool_fwd(PoolGeom g, const T* __res
         if (ky < ky0 || ky >= ky1 || kx < kx0 || kx >= kx1) continue;
         float v[V];
         Vec<T>::unpack(raw[ky * KC + kx], v);
+        act(v);
 #pragma unroll
         for (int j = 0; j < V; ++j)
           if (v[j] > m[j] || isnan(v[j])) m[j] = v[j], id[j] = ky * KC + kx;
@@ -358,6 +527,7 @@ __global__ void __launch_bounds__(kBlk) k_maxpool_fwd(PoolGeom g, const T* __res
       for (int kx = kx0; kx < kx1; ++kx) {
         float v[V];
         Vec<T>::unpack(*reinterpret_cast<const R*>(row + (x0 + kx) * g.c), v);
+        act(v);
 #pragma unroll
         for (int j = 0; j < V; ++j)
           if (v[j] > m[j] || isnan(v[j])) m[j] = v[j], id[j] = ky * g.k + kx;
@@ -476,16 +646,17 @@ inline bool pool_grid(PoolGeom& g, int V) {
 }
 
 template <typename T>
-int maxpool(const PoolGeom& g, const void* x, void* y, void* idx, hipStream_t st) {
+int maxpool(const PoolGeom& g, const void* x, const void* b, void* y, void* idx, hipStream_t st) {
   constexpr int V = Vec<T>::N;
-  if (g.c % V || !al16(x) || !al16(y) || ((uintptr_t)idx & (V - 1))) return WAM_ERR_UNSUPPORTED;
+  if (g.c % V || !al16(x) || !al16(b) || !al16(y) || ((uintptr_t)idx & (V - 1))) return WAM_ERR_UNSUPPORTED;
   PoolGeom gg = g;
   if (!pool_grid(gg, V)) return WAM_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((gg.wo * gg.cv + kBlk - 1) / kBlk), (unsigned)gg.ho, (unsigned)gg.n);
-  if (gg.k == 3)
-    hipLaunchKernelGGL((k_maxpool_fwd<T, 3>), grid, kBlk, 0, st, gg, (const T*)x, (T*)y, (uint8_t*)idx);
-  else
-    hipLaunchKernelGGL((k_maxpool_fwd<T, 0>), grid, kBlk, 0, st, gg, (const T*)x, (T*)y, (uint8_t*)idx);
+  const T *xp = (const T*)x, *bp = (const T*)b;
+  if (gg.k == 3 && b) hipLaunchKernelGGL((k_maxpool_fwd<T, 3, true>), grid, kBlk, 0, st, gg, xp, bp, (T*)y, (uint8_t*)idx);
+  else if (b) hipLaunchKernelGGL((k_maxpool_fwd<T, 0, true>), grid, kBlk, 0, st, gg, xp, bp, (T*)y, (uint8_t*)idx);
+  else if (gg.k == 3) hipLaunchKernelGGL((k_maxpool_fwd<T, 3, false>), grid, kBlk, 0, st, gg, xp, bp, (T*)y, (uint8_t*)idx);
+  else hipLaunchKernelGGL((k_maxpool_fwd<T, 0, false>), grid, kBlk, 0, st, gg, xp, bp, (T*)y, (uint8_t*)idx);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -557,8 +728,47 @@ int wam_ew_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, i
       (dtype != WAM_DT_F32 && dtype != WAM_DT_BF16))
     return WAM_ERR_INVALID_ARG;
   if (n == 0) return WAM_OK;
-  return dtype == WAM_DT_F32 ? maxpool<float>(g, x, y, idx, (hipStream_t)stream)
-                             : maxpool<uint16_t>(g, x, y, idx, (hipStream_t)stream);
+  return dtype == WAM_DT_F32 ? maxpool<float>(g, x, nullptr, y, idx, (hipStream_t)stream)
+                             : maxpool<uint16_t>(g, x, nullptr, y, idx, (hipStream_t)stream);
+}
+
+int wam_ew_bias_maxpool_nhwc(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride, int pad,
+                             const void* x, const void* bias, void* y, void* idx, void* stream) {
+  PoolGeom g;
+  if (!pool_geom(g, n, h, w, c, k, stride, pad) || !bias || (n > 0 && (!x || !y || !idx)) ||
+      (dtype != WAM_DT_F32 && dtype != WAM_DT_BF16))
+    return WAM_ERR_INVALID_ARG;
+  if (n == 0) return WAM_OK;
+  return dtype == WAM_DT_F32 ? maxpool<float>(g, x, bias, y, idx, (hipStream_t)stream)
+                             : maxpool<uint16_t>(g, x, bias, y, idx, (hipStream_t)stream);
+}
+
+int wam_ew_bias_act_bits(int dtype, int64_t n, int64_t channels, int64_t inner, void* y, const void* bias, void* mask,
+                         void* stream) {
+  if (n < 0 || channels < 1 || inner < 1 || (n > 0 && (!y || !mask)) || (dtype != WAM_DT_F32 && dtype != WAM_DT_BF16))
+    return WAM_ERR_INVALID_ARG;
+  if (dtype != WAM_DT_BF16) return WAM_ERR_UNSUPPORTED;
+  if (n == 0) return WAM_OK;
+  return bias_act_bits(n, channels, inner, y, bias, mask, (hipStream_t)stream);
+}
+
+int wam_ew_add_bias_relu_bits(int dtype, int64_t n, int64_t channels, int64_t inner, const void* a, const void* bias_a,
+                              const void* s, const void* bias_s, void* out, void* mask, void* stream) {
+  if (n < 0 || channels < 1 || inner < 1 || (n > 0 && (!a || !s || !out || !mask)) ||
+      (dtype != WAM_DT_F32 && dtype != WAM_DT_BF16))
+    return WAM_ERR_INVALID_ARG;
+  if (dtype != WAM_DT_BF16) return WAM_ERR_UNSUPPORTED;
+  if (n == 0) return WAM_OK;
+  return add_bias_relu_bits(n, channels, inner, a, bias_a, s, bias_s, out, mask, (hipStream_t)stream);
+}
+
+int wam_ew_relu_mask_bits(int dtype, int64_t n, const void* g1, const void* g2, const void* mask, void* out,
+                          void* stream) {
+  if (n < 0 || (n > 0 && (!g1 || !mask || !out)) || (dtype != WAM_DT_F32 && dtype != WAM_DT_BF16))
+    return WAM_ERR_INVALID_ARG;
+  if (dtype != WAM_DT_BF16) return WAM_ERR_UNSUPPORTED;
+  if (n == 0) return WAM_OK;
+  return relu_mask_bits(n, g1, g2, mask, out, (hipStream_t)stream);
 }
 
 int wam_ew_maxpool_nhwc_backward(int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int stride, int pad,

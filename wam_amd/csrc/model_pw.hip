@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "relubits.hpp"
 
 namespace {
 
@@ -76,14 +77,21 @@ __device__ __forceinline__ uint4 pack8_relu(const float (&v)[8]) {
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+
 constexpr int PW_TAIL = WAM_PW_TAIL, PW_MASK = WAM_PW_MASK;
 
 // HAS_G2: PW_MASK with a second gradient. r0 = s (TAIL) / g2 (MASK), r1 = y (MASK).
-template <int K, int N, int NS, int WAVES, int MINW, int D, int MODE, bool HAS_G2>
+// BITS (WAM_PW_BITS): `bits` is the packed ReLU mask, one bit per element of [M, N] -- written from
+// the stored output in PW_TAIL, read in place of y in PW_MASK (r1 is then unused). A pixel's 64-column
+// chunk is 8 mask bytes, of which lane half h holds bytes 2 j + h: the halves are combined so that
+// the mask moves as one 8-byte access per pixel and chunk. (Collecting a round of D chunks into one
+// 16-byte store per lane, with the bit taken from the fp32 sum, was tried: 168 VGPRs and scratch at
+// K = 64, so it is not used.)
+template <int K, int N, int NS, int WAVES, int MINW, int D, int MODE, bool HAS_G2, bool BITS>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(MINW)))
     k_pw_gemm(int64_t M, const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
               const uint16_t* __restrict__ ba, const uint16_t* __restrict__ bs, const uint16_t* __restrict__ r0,
-              const uint16_t* __restrict__ r1, uint16_t* __restrict__ out, int rounded) {
+              const uint16_t* __restrict__ r1, uint8_t* bits, uint16_t* __restrict__ out, int rounded) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int NL = N / NS;      // this workgroup's columns
   constexpr int LDW = K + 8;      // LDS row of W in bf16 elements (16 bytes of padding)
@@ -121,12 +129,14 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   constexpr int NCH = NL / 64;  // 64-column chunks
   static_assert(NCH % D == 0, "the operand ring holds a whole number of rounds per tile");
   // a chunk's epilogue operands: 4 x 16 bytes per tensor and lane, channel nc*64 + 16 j + 8 h
-  auto load_e = [&](int64_t o, uint4 (&e0)[4], uint4 (&e1)[4]) {
+  // (with BITS the y operand is the pixel's 8 mask bytes of the chunk, the same in both lane halves)
+  auto load_e = [&](int64_t o, uint4 (&e0)[4], uint4 (&e1)[4], uint2& eb) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (MODE == PW_TAIL || HAS_G2) e0[j] = *reinterpret_cast<const uint4*>(r0 + o + j * 16);
-      if (MODE == PW_MASK) e1[j] = *reinterpret_cast<const uint4*>(r1 + o + j * 16);
+      if (MODE == PW_MASK && !BITS) e1[j] = *reinterpret_cast<const uint4*>(r1 + o + j * 16);
     }
+    if (MODE == PW_MASK && BITS) eb = *reinterpret_cast<const uint2*>(bits + (o >> 3) - h);
   };
   auto row_of = [&](int64_t tile) {
     const int64_t m = tile * TM + wave * 32 + r;
@@ -136,10 +146,11 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   // ring of D chunk buffers: chunk c lives in buffer c % D and is reloaded with chunk c + D (of
   // this tile or the next) as soon as its epilogue has consumed it, so D - 1 chunks are in flight
   uint4 xf[KS], e0[D][4], e1[D][4];
+  uint2 eb[D];
   if ((int64_t)blockIdx.x < tiles) {
     load_x(blockIdx.x, xf);
 #pragma unroll
-    for (int d = 0; d < D; ++d) load_e(row_of(blockIdx.x) + d * 64, e0[d], e1[d]);
+    for (int d = 0; d < D; ++d) load_e(row_of(blockIdx.x) + d * 64, e0[d], e1[d], eb[d]);
   }
 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -196,7 +207,13 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
               res[j] = pack8_relu(v);  // NaN propagates, as in k_add_bias_relu (fmaxf would return 0)
             } else {
               float yv[8], gv[8];
-              unpack8(e1[d][j], yv);
+              if constexpr (BITS) {  // byte 2 j + h of the 8: bit i set = y > 0
+                const uint32_t mb = (j < 2 ? eb[d].x : eb[d].y) >> (16 * (j & 1) + 8 * h);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) yv[i] = (mb >> i) & 1u ? 1.f : 0.f;
+              } else {
+                unpack8(e1[d][j], yv);
+              }
               if (HAS_G2) unpack8(e0[d][j], gv);
 #pragma unroll
               for (int i = 0; i < 8; ++i) v[i] = yv[i] > 0.f ? (HAS_G2 ? v[i] + gv[i] : v[i]) : 0.f;
@@ -204,10 +221,21 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
             }
           }
         const int nn = nc + D;
-        load_e(nn < NCH ? row + nn * 64 : row_next + (nn - NCH) * 64, e0[d], e1[d]);
+        load_e(nn < NCH ? row + nn * 64 : row_next + (nn - NCH) * 64, e0[d], e1[d], eb[d]);
         if (live) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) *reinterpret_cast<uint4*>(out + row + nc * 64 + j * 16) = res[j];
+        }
+        if constexpr (MODE == PW_TAIL && BITS) {
+          // this lane's bytes 2 j + h; the swap hands every lane both halves' words of its pixel
+          const uint32_t mine = wam_pos_bits(res[0]) | (wam_pos_bits(res[1]) << 8) | (wam_pos_bits(res[2]) << 16) |
+                                (wam_pos_bits(res[3]) << 24);
+          const auto pr = __builtin_amdgcn_permlane32_swap(mine, mine, false, false);
+          const uint32_t ev = pr[0], od = pr[1];  // bytes 0 2 4 6 and 1 3 5 7
+          uint2 mk;
+          mk.x = (ev & 0xffu) | ((od & 0xffu) << 8) | ((ev & 0xff00u) << 8) | ((od & 0xff00u) << 16);
+          mk.y = ((ev >> 16) & 0xffu) | (((od >> 16) & 0xffu) << 8) | ((ev >> 24) << 16) | ((od >> 24) << 24);
+          if (live && h == 0) *reinterpret_cast<uint2*>(bits + ((row + nc * 64) >> 3)) = mk;
         }
       }
     }
@@ -234,22 +262,24 @@ int resident_wgs(int per_cu) {
 // tail, mask + g2 and mask kernels
 template <int K, int N, int NS, int WAVES, int PER_CU, int MINW, int DT, int DM2, int DM1>
 int launch(int mode, int64_t M, const uint16_t* x, const uint16_t* w, const uint16_t* ba, const uint16_t* bs,
-           const uint16_t* r0, const uint16_t* r1, uint16_t* out, int rounded, int max_wgs, hipStream_t st) {
+           const uint16_t* r0, const uint16_t* r1, uint8_t* bits, uint16_t* out, int rounded, int max_wgs,
+           hipStream_t st) {
   const int64_t tiles = (M + 32 * WAVES - 1) / (32 * WAVES);
   int64_t gx = resident_wgs(PER_CU) / NS;
   if (max_wgs > 0) gx = max_wgs;
   if (gx > tiles) gx = tiles;
   if (gx < 1) gx = 1;
   const dim3 grid((unsigned)gx, NS), block(WAVES * 64);
-  if (mode == PW_TAIL)
-    hipLaunchKernelGGL((k_pw_gemm<K, N, NS, WAVES, MINW, DT, PW_TAIL, false>), grid, block, 0, st, M, x, w, ba, bs, r0,
-                       r1, out, rounded);
-  else if (r0)
-    hipLaunchKernelGGL((k_pw_gemm<K, N, NS, WAVES, MINW, DM2, PW_MASK, true>), grid, block, 0, st, M, x, w, ba, bs, r0,
-                       r1, out, rounded);
-  else
-    hipLaunchKernelGGL((k_pw_gemm<K, N, NS, WAVES, MINW, DM1, PW_MASK, false>), grid, block, 0, st, M, x, w, ba, bs,
-                       r0, r1, out, rounded);
+#define WAM_PW_LAUNCH(DD, MODE_, G2, B) \
+  hipLaunchKernelGGL((k_pw_gemm<K, N, NS, WAVES, MINW, DD, MODE_, G2, B>), grid, block, 0, st, M, x, w, ba, bs, r0, r1, \
+                     bits, out, rounded)
+  if (mode == PW_TAIL && bits) WAM_PW_LAUNCH(DT, PW_TAIL, false, true);
+  else if (mode == PW_TAIL) WAM_PW_LAUNCH(DT, PW_TAIL, false, false);
+  else if (r0 && bits) WAM_PW_LAUNCH(DM2, PW_MASK, true, true);
+  else if (r0) WAM_PW_LAUNCH(DM2, PW_MASK, true, false);
+  else if (bits) WAM_PW_LAUNCH(DM1, PW_MASK, false, true);
+  else WAM_PW_LAUNCH(DM1, PW_MASK, false, false);
+#undef WAM_PW_LAUNCH
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }
@@ -265,10 +295,14 @@ int wam_pw_supported(int dtype, int64_t K, int64_t N) {
 int wam_pw_gemm_ex(int mode, int64_t M, int64_t K, int64_t N, const void* x, const void* w, const void* bias_a,
                    const void* bias_b, const void* r0, const void* r1, void* out, int max_workgroups, void* stream) {
   const int rounded = (mode & WAM_PW_ROUNDED) ? 1 : 0;
-  if (mode >= 0) mode &= ~WAM_PW_ROUNDED;
+  // WAM_PW_BITS: r1 is the packed mask. The signature is pinned, so r1 stays `const void*` although
+  // PW_TAIL WRITES the mask through it (include/wam_hip.h says so); the kernel gets it as the separate,
+  // non-const and non-restrict `bits` pointer and a NULL r1.
+  const bool packed = mode >= 0 && (mode & WAM_PW_BITS);
+  if (mode >= 0) mode &= ~(WAM_PW_ROUNDED | WAM_PW_BITS);
   if (M <= 0 || !x || !w || !out || (mode != WAM_PW_TAIL && mode != WAM_PW_MASK) || max_workgroups < 0)
     return WAM_ERR_INVALID_ARG;
-  if ((mode == WAM_PW_TAIL && (!r0 || r1)) || (mode == WAM_PW_MASK && (!r1 || bias_a || bias_b)))
+  if ((mode == WAM_PW_TAIL && (!r0 || (r1 != nullptr) != packed)) || (mode == WAM_PW_MASK && (!r1 || bias_a || bias_b)))
     return WAM_ERR_INVALID_ARG;
   if (!wam_pw_supported(WAM_DT_BF16, K, N)) return WAM_ERR_UNSUPPORTED;
   if (M > (int64_t(1) << 52)) return WAM_ERR_UNSUPPORTED;
@@ -276,14 +310,15 @@ int wam_pw_gemm_ex(int mode, int64_t M, int64_t K, int64_t N, const void* x, con
   for (const void* p : {x, w, r0, r1, (const void*)out})
     if (p && !al16(p)) return WAM_ERR_UNSUPPORTED;
   const uint16_t *xp = (const uint16_t*)x, *wp = (const uint16_t*)w, *ba = (const uint16_t*)bias_a,
-                 *bs = (const uint16_t*)bias_b, *p0 = (const uint16_t*)r0, *p1 = (const uint16_t*)r1;
+                 *bs = (const uint16_t*)bias_b, *p0 = (const uint16_t*)r0, *p1 = packed ? nullptr : (const uint16_t*)r1;
+  uint8_t* pb = packed ? (uint8_t*)r1 : nullptr;
   hipStream_t st = (hipStream_t)stream;
   uint16_t* op = (uint16_t*)out;
   // measured on MI355X (scripts/kbench_pointwise.py): K = 64 three workgroups of 4
   // waves per CU, K = 128 one workgroup of 8 waves holding all of W; operand ring as deep as the
   // registers allow without scratch
-  if (K == 64) return launch<64, 256, 1, 4, 3, 3, 2, 2, 2>(mode, M, xp, wp, ba, bs, p0, p1, op, rounded, max_workgroups, st);
-  return launch<128, 512, 1, 8, 1, 2, 4, 2, 4>(mode, M, xp, wp, ba, bs, p0, p1, op, rounded, max_workgroups, st);
+  if (K == 64) return launch<64, 256, 1, 4, 3, 3, 2, 2, 2>(mode, M, xp, wp, ba, bs, p0, p1, pb, op, rounded, max_workgroups, st);
+  return launch<128, 512, 1, 8, 1, 2, 4, 2, 4>(mode, M, xp, wp, ba, bs, p0, p1, pb, op, rounded, max_workgroups, st);
 }
 
 int wam_pw_gemm(int mode, int dtype, int64_t M, int64_t K, int64_t N, const void* x, const void* w,

@@ -18,6 +18,10 @@ rewrites the traced graph so each chain is one HIP kernel (wam_amd/csrc/model_ew
   input-gradient GEMM carries the producer's ReLU mask and the parked skip gradient as its epilogue.
 * the polyphase input convolution (``model_opt.InputConv2d``) followed by a ReLU gets the same
   bias + ReLU epilogue and a masked polyphase backward.
+* in bf16 the ReLU producers also write one bit per element (out > 0) and the backward masks read
+  that bit instead of the activation; where a fused tail's output feeds a downsample block, a
+  ``GradFork`` hands it to both users so that the two gradients are summed under the producer's
+  mask in one launch; the stem's max pool applies bias + ReLU to what it loads (``RELU_BITS``).
 
 Only the pattern's own nodes are touched; everything else runs as traced. The functions are the
 same as the graph's up to fp rounding (the bf16 tail sum rounds once instead of three times);
@@ -25,6 +29,7 @@ tests/test_model_opt.py compares outputs and input gradients with the unfused mo
 There is no CPU path for the fused ops: on a CPU model the rewrite is not applied.
 """
 import operator
+import os
 
 import torch
 import torch.fx as fx
@@ -35,6 +40,12 @@ from . import _lib
 from .model_opt import InputConv2d, _PolyphaseInputGrad  # noqa: F401
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
+_UNSUPPORTED = 3  # WAM_ERR_UNSUPPORTED: the operands are not ones the entry serves, nothing was written
+
+# Packed ReLU masks, junction forks and the stem's fused bias + ReLU + pool. One
+# switch for all three, read at every call: off (or WAM_MODEL_RELU_BITS=0) the model runs the
+# activation-reading kernels and autograd's own gradient sums, with the same results bit for bit.
+RELU_BITS = os.environ.get("WAM_MODEL_RELU_BITS", "1") != "0"
 
 
 def _dt(t):
@@ -98,6 +109,74 @@ def relu_mask(g, y, g2=None):
     return out
 
 
+def _is_cl(t):
+    """The dense layout _like(., t) produces is channels_last (else plain contiguous)."""
+    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
+
+
+def _dense(t, cl):
+    return t.contiguous(memory_format=torch.channels_last) if cl else t.contiguous()
+
+
+def _bits_ok(t):
+    return RELU_BITS and t.dtype == torch.bfloat16 and t.numel() > 0 and t.numel() % 8 == 0
+
+
+def _new_bits(t):
+    return torch.empty(t.numel() // 8, dtype=torch.uint8, device=t.device)
+
+
+def bias_relu_bits_(y, b):
+    """bias_act_(y, b, True) -> (y, packed mask of y > 0); the mask is None where the bits form does
+    not serve the operands (or is switched off) and the plain kernel ran."""
+    y, inner = _layout(y)
+    if _bits_ok(y):
+        bits = _new_bits(y)
+        rc = _lib.lib.wam_ew_bias_act_bits(_dt(y), y.numel(), y.shape[1], inner, _lib.ptr(y),
+                                           _lib.ptr(b.to(y.dtype).contiguous() if b is not None else None),
+                                           _lib.ptr(bits), _stream(y))
+        if rc == 0:
+            return y, bits
+        if rc != _UNSUPPORTED:
+            _lib.check(rc)
+    return bias_act_(y, b, True), None
+
+
+def add_bias_relu_bits(a, ba, s, bs):
+    """add_bias_relu(a, ba, s, bs) -> (out, packed mask of out > 0 or None, as bias_relu_bits_)."""
+    if _bits_ok(a):
+        a, inner = _layout(a)
+        s = _like(s, a)
+        out = torch.empty_like(a)
+        bits = _new_bits(a)
+        cast = (lambda b: None if b is None else b.to(a.dtype).contiguous())
+        rc = _lib.lib.wam_ew_add_bias_relu_bits(_dt(a), a.numel(), a.shape[1], inner, _lib.ptr(a), _lib.ptr(cast(ba)),
+                                                _lib.ptr(s), _lib.ptr(cast(bs)), _lib.ptr(out), _lib.ptr(bits),
+                                                _stream(a))
+        if rc == 0:
+            return out, bits
+        if rc != _UNSUPPORTED:
+            _lib.check(rc)
+    return add_bias_relu(a, ba, s, bs), None
+
+
+def relu_mask_bits(g, bits, cl, g2=None):
+    """bit ? g (+ g2) : 0 with the producer's packed mask; cl: the producer's output was channels_last
+    (the mask is indexed flat in that layout, so g and g2 are made dense in it)."""
+    g = _dense(g, cl)
+    g2 = None if g2 is None else _dense(g2, cl)
+    for retry in (False, True):
+        if retry:  # a gradient view at an odd storage offset: fresh allocations are aligned
+            g, g2 = g.clone(), (None if g2 is None else g2.clone())
+        out = torch.empty_like(g)
+        rc = _lib.lib.wam_ew_relu_mask_bits(_dt(g), g.numel(), _lib.ptr(g), _lib.ptr(g2), _lib.ptr(bits),
+                                            _lib.ptr(out), _stream(g))
+        if rc != _UNSUPPORTED:
+            break
+    _lib.check(rc)
+    return out
+
+
 def _pool_ok(y, k, s, p):
     v = 8 if y.dtype == torch.bfloat16 else 4
     return (y.is_cuda and y.dim() == 4 and y.dtype in _DT and y.shape[1] % v == 0 and 2 * p <= k and k * k <= 127
@@ -113,6 +192,21 @@ def maxpool_nhwc(y, k, s, p):
     idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=y.device)
     _lib.check(_lib.lib.wam_ew_maxpool_nhwc(_dt(y), n, h, w, c, k, s, p, _lib.ptr(y), _lib.ptr(out), _lib.ptr(idx),
                                             _stream(y)))
+    return out, idx
+
+
+def bias_relu_maxpool_nhwc(x, b, k, s, p):
+    """maxpool_nhwc(bias_act_(x, b, True), k, s, p) in one launch, x left as it is; None where the
+    kernel does not serve the operands."""
+    n, c, h, w = x.shape
+    ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+    out = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device)
+    rc = _lib.lib.wam_ew_bias_maxpool_nhwc(_dt(x), n, h, w, c, k, s, p, _lib.ptr(x), _lib.ptr(b.to(x.dtype).contiguous()),
+                                           _lib.ptr(out), _lib.ptr(idx), _stream(x))
+    if rc == _UNSUPPORTED:
+        return None
+    _lib.check(rc)
     return out, idx
 
 
@@ -179,6 +273,7 @@ _PW_TAIL, _PW_MASK = 0, 1
 # for bit, profiles/r07b_dump_compare.log); applied to the unrounded accumulator the random-init bf16
 # ResNet-50's ReLU masks flip and the maps move by 8e-2 relative L2
 _PW_ROUNDED = 16
+_PW_BITS = 32  # r1 is the packed ReLU mask of [M, N]: PW_TAIL writes it, PW_MASK reads it in place of y
 # (mode, K, N) served by the fused kernel: the pairs that beat torch.mm + the wam_ew_* pass on
 # MI355X (scripts/kbench_pointwise.py); anything else stays on the two-kernel path
 _PW_ROUTES = {(_PW_TAIL, 64, 256), (_PW_TAIL, 128, 512), (_PW_MASK, 64, 256), (_PW_MASK, 128, 512)}
@@ -190,7 +285,8 @@ def _pw_routed(mode, w2):
 
 
 def pw_gemm(mode, x2, w2, ba=None, bs=None, r0=None, r1=None):
-    """epilogue(x2 [M, K] @ w2 [N, K]^T) -> [M, N]; PW_TAIL: r0 = s, PW_MASK: r0 = g2 or None, r1 = y."""
+    """epilogue(x2 [M, K] @ w2 [N, K]^T) -> [M, N]; PW_TAIL: r0 = s, PW_MASK: r0 = g2 or None, r1 = y.
+    mode | _PW_BITS: r1 is the packed mask of [M, N] -- written by PW_TAIL, read for y by PW_MASK."""
     m, k = x2.shape
     n = w2.shape[0]
     out = torch.empty((m, n), dtype=x2.dtype, device=x2.device)
@@ -231,12 +327,14 @@ class _SkipGrad:
     says the consumer add took the box, i.e. a skip gradient will be parked. torch.addmm cannot
     do this: it copies its C operand into the output first (scripts/skip_ab.py)."""
 
-    __slots__ = ("g", "armed", "final")
+    __slots__ = ("g", "armed", "final", "bits", "cl")
 
     def __init__(self):
         self.g = None
         self.armed = False
         self.final = False
+        self.bits = None  # the producer's packed mask and its layout, for a _GradForkFn on its output
+        self.cl = False
 
 
 class _SkipLink:
@@ -247,15 +345,18 @@ class _SkipLink:
         self.cur = None
 
 
-def _masked_sum(take, g, out):
+def _masked_sum(take, g, out, bits=None, cl=False):
     """The producer's ReLU mask over g + the parked skip gradient -- or g as it is when the consumer's
-    conv1 backward already applied both (PW_MASK) and marked the box final."""
+    conv1 backward (PW_MASK) or the fork on the producer's output already applied both and marked
+    the box final. The mask is the packed one (bits, cl) where the producer wrote it, else out > 0."""
     g2 = None
     if take is not None:
         if take.final:
             take.final = False
-            return _like(g, out)
+            return _dense(g, cl) if bits is not None else _like(g, out)
         g2, take.g = take.g, None
+    if bits is not None:
+        return relu_mask_bits(g, bits, cl, g2)
     return relu_mask(g, out, g2)
 
 
@@ -272,13 +373,15 @@ class _ConvBiasReLUFn(torch.autograd.Function):
                 # x is the linked producer's output: its mask and the skip gradient parked in the
                 # box become the epilogue of this convolution's input-gradient GEMM
                 ctx.box = box
-                ctx.save_for_backward(w2, y, wt, x)
+                ctx.xbits, ctx.xshape = box.bits is not None, x.shape
+                ctx.save_for_backward(w2, y, wt, box.bits if ctx.xbits else x)
             else:
                 ctx.save_for_backward(w2, y)
             return y
-        y = bias_act_(_conv_nd(x, w, *geom), b, True)
-        ctx.save_for_backward(x, w, y)
-        ctx.geom = geom
+        y, bits = bias_relu_bits_(_conv_nd(x, w, *geom), b)
+        ctx.cl = bits is not None and _is_cl(y)  # with the packed mask, y itself is not kept
+        ctx.save_for_backward(x, w, y if bits is None else bits)
+        ctx.geom, ctx.bits = geom, bits is not None
         return y
 
     @staticmethod
@@ -297,11 +400,16 @@ class _ConvBiasReLUFn(torch.autograd.Function):
                 g2 = _rows(box.g)
                 if g2 is not None and g2.dtype == gm.dtype:
                     box.g, box.final = None, True
-                    dx = pw_gemm(_PW_MASK, _rows(gm), wt, None, None, g2, _rows(x))
-                    return _unrows(dx, x), None, None, None, None, None
+                    if ctx.xbits:  # x holds the producer's packed mask, not its output
+                        dx = pw_gemm(_PW_MASK | _PW_BITS, _rows(gm), wt, None, None, g2, x)
+                    else:
+                        dx = pw_gemm(_PW_MASK, _rows(gm), wt, None, None, g2, _rows(x))
+                    n, _, h, ww = ctx.xshape
+                    return dx.view(n, h, ww, dx.shape[1]).permute(0, 3, 1, 2), None, None, None, None, None
             return _unrows(torch.mm(_rows(gm), w2), y), None, None, None, None, None
         x, w, y = ctx.saved_tensors
-        return _conv_grad_input(relu_mask(g, y), x, w, *ctx.geom), None, None, None, None, None
+        gm = relu_mask_bits(g, y, ctx.cl) if ctx.bits else relu_mask(g, y)
+        return _conv_grad_input(gm, x, w, *ctx.geom), None, None, None, None, None
 
 
 class _PointwiseConvFn(torch.autograd.Function):
@@ -329,15 +437,19 @@ class _PointwiseConvFn(torch.autograd.Function):
 class _AddBiasReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, ba, s, bs, park=None, take=None):
-        out = add_bias_relu(a, ba, s, bs)
-        ctx.save_for_backward(out)
-        ctx.park, ctx.take = park, take
+        out, bits = add_bias_relu_bits(a, ba, s, bs)
+        ctx.cl = bits is not None and _is_cl(out)
+        ctx.save_for_backward(out if bits is None else bits)
+        ctx.park, ctx.take, ctx.bits = park, take, bits is not None
+        if take is not None:
+            take.bits, take.cl = bits, ctx.cl
         return out
 
     @staticmethod
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
-        gm = _masked_sum(ctx.take, g, out)  # skip gradient of the consumer block, summed under the mask
+        # skip gradient of the consumer block, summed under the mask
+        gm = _masked_sum(ctx.take, g, out, out if ctx.bits else None, ctx.cl)
         if ctx.park is not None:  # s was passed detached: its gradient goes to s's producer
             ctx.park.g = gm
             return gm, None, None, None, None, None
@@ -350,20 +462,56 @@ class _PWTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w2, ba, s, bs, park=None, take=None):
-        out = _unrows(pw_gemm(_PW_TAIL, _rows(x), w2, ba, bs, _rows(s)), s)
-        ctx.save_for_backward(w2, out)
-        ctx.park, ctx.take = park, take
+        bits = _new_bits(s) if _bits_ok(s) else None
+        if bits is None:
+            out = _unrows(pw_gemm(_PW_TAIL, _rows(x), w2, ba, bs, _rows(s)), s)
+        else:
+            out = _unrows(pw_gemm(_PW_TAIL | _PW_BITS, _rows(x), w2, ba, bs, _rows(s), bits), s)
+        ctx.cl = bits is not None and _is_cl(out)
+        ctx.save_for_backward(w2, out if bits is None else bits)
+        ctx.park, ctx.take, ctx.bits, ctx.shape = park, take, bits is not None, out.shape
+        if take is not None:
+            take.bits, take.cl = bits, ctx.cl
         return out
 
     @staticmethod
     def backward(ctx, g):
         w2, out = ctx.saved_tensors
-        gm = _masked_sum(ctx.take, g, out)
-        dx = _unrows(torch.mm(_rows(gm), w2), out)
+        gm = _masked_sum(ctx.take, g, out, out if ctx.bits else None, ctx.cl)
+        n, _, h, ww = ctx.shape
+        dx = torch.mm(_rows(gm), w2).view(n, h, ww, w2.shape[1]).permute(0, 3, 1, 2)
         if ctx.park is not None:
             ctx.park.g = gm
             return dx, None, None, None, None, None, None
         return dx, None, None, gm, None, None, None
+
+
+class _GradForkFn(torch.autograd.Function):
+    """A fused tail's output handed to its two users (a downsample block's conv1 and its shortcut
+    convolution) as two outputs, so that the backward receives both gradients -- autograd calls it
+    only when both have arrived -- and runs the producer's ReLU mask over their sum in ONE launch:
+    without it autograd sums them with a torch add (3 passes) before the producer's mask (3 passes).
+    bf16(g1 + g2) rounds once either way and the mask only selects, so the bits are the same. The
+    box is marked final: the producer's backward passes the result on as it is."""
+
+    @staticmethod
+    def forward(ctx, x, box):
+        ctx.box = box
+        ctx.bits, ctx.cl = box.bits is not None, box.cl
+        ctx.save_for_backward(box.bits if ctx.bits else x)
+        ctx.set_materialize_grads(False)
+        return x.view_as(x), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        if g1 is None:
+            g1, g2 = g2, None
+        if g1 is None:
+            return None, None
+        (y,) = ctx.saved_tensors
+        gm = relu_mask_bits(g1, y, ctx.cl, g2) if ctx.bits else relu_mask(g1, y, g2)
+        ctx.box.final = True
+        return gm, None
 
 
 class _PolyphaseReLUFn(torch.autograd.Function):
@@ -395,9 +543,16 @@ class _PolyphaseReLUPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, wpoly, pad, geom, pool):
-        y = bias_act_(F.conv2d(x, weight, None, 2, pad), bias, True)
+        y = F.conv2d(x, weight, None, 2, pad)
         k, s, p = pool
         ctx.geom, ctx.in_hw, ctx.pool, ctx.y_shape = geom, x.shape[-2:], pool, y.shape
+        # the pool applies bias + ReLU to what it loads: the biased tensor is never written
+        fused = bias_relu_maxpool_nhwc(y, bias, k, s, p) if RELU_BITS and _pool_ok(y, k, s, p) else None
+        if fused is not None:
+            ctx.save_for_backward(wpoly, fused[1])
+            ctx.hip = True
+            return fused[0]
+        y = bias_act_(y, bias, True)
         if _pool_ok(y, k, s, p):
             out, idx = maxpool_nhwc(y, k, s, p)
             ctx.save_for_backward(wpoly, idx)
@@ -491,6 +646,7 @@ class AddBiasReLU(nn.Module):
 
         self.link_in = None   # _SkipLink: operand s comes from a linked producer (park its gradient)
         self.link_out = None  # _SkipLink: this output is a linked consumer's skip operand (take it)
+        self.fork_out = None  # _SkipLink: this output goes through a GradFork (it applies this mask)
 
     def _fusable(self, a, s):
         """The HIP kernel indexes s with a's flat index: same shape, dtype, layout and device only."""
@@ -526,6 +682,8 @@ class AddBiasReLU(nn.Module):
                 self.link_out.cur = None
             if self.link_in is not None:
                 self.link_in.cur = None
+            if self.fork_out is not None:
+                self.fork_out.cur = None
             bias = (lambda t, b: t if b is None else t + b.to(t.dtype).view((1, -1) + (1,) * (t.dim() - 2)))
             return torch.relu(bias(a, self.bias_a) + bias(s, self.bias_s))
         park = take = None
@@ -536,9 +694,30 @@ class AddBiasReLU(nn.Module):
         if self.link_out is not None:
             grad = torch.is_grad_enabled() and (a.requires_grad or s.requires_grad)
             take = self.link_out.cur = _SkipGrad() if grad else None
+        elif self.fork_out is not None:
+            grad = RELU_BITS and torch.is_grad_enabled() and (a.requires_grad or s.requires_grad)
+            take = self.fork_out.cur = _SkipGrad() if grad else None
         if pending is not None:
             return _PWTailFn.apply(a, pending.w2, self.bias_a, s, self.bias_s, park, take)
         return _AddBiasReLUFn.apply(a, self.bias_a, s, self.bias_s, park, take)
+
+
+class GradFork(nn.Module):
+    """x -> (x, x) for the two users of a fused tail's output at a downsample junction; with grad on
+    a CUDA tensor the pair comes from _GradForkFn, whose backward fuses the gradient sum into the
+    producer's ReLU mask. Anything else (no grad, CPU, an unfused producer) gets x twice."""
+
+    def __init__(self):
+        super().__init__()
+        self.src = None  # _SkipLink to the producing AddBiasReLU (its fork_out)
+
+    def forward(self, x):
+        box = None
+        if self.src is not None:
+            box, self.src.cur = self.src.cur, None
+        if box is None or not torch.is_grad_enabled() or not x.is_cuda or not x.requires_grad:
+            return x, x
+        return _GradForkFn.apply(x, box)
 
 
 class InputConvReLU(nn.Module):
@@ -696,6 +875,7 @@ def fuse_elementwise(gm):
         g.erase_node(src)
         count += 1
     _link_skip_gradients(gm, mods)
+    _fork_junction_gradients(gm, mods, add_mod)
     g.lint()
     gm.recompile()
     gm.delete_all_unused_submodules()
@@ -714,6 +894,17 @@ def _reaches(src, dst):
         seen.add(n)
         stack.extend(n.users)
     return False
+
+
+def _descendants(src):
+    """src and every fx node that uses it, directly or not."""
+    seen, stack = set(), [src]
+    while stack:
+        n = stack.pop()
+        if n not in seen:
+            seen.add(n)
+            stack.extend(n.users)
+    return seen
 
 
 def _link_skip_gradients(gm, mods):
@@ -742,3 +933,48 @@ def _link_skip_gradients(gm, mods):
             mods[other[0].target].link_src = link  # the block's conv1: fused mask backward
         links += 1
     return links
+
+
+def _fork_junction_gradients(gm, mods, add_mod):
+    """Route each AddBiasReLU output with exactly two users whose branches meet, one per operand, in
+    the nearest later AddBiasReLU (a downsample block: conv1 towards operand a, the shortcut
+    convolution towards s) through a GradFork. The identity-skip pattern (one user IS the add) is
+    _link_skip_gradients' and is left alone. Not a fusion of forward nodes, so it is not counted as
+    one. (The fork itself is right for any two users: it only sums two gradients under the
+    producer's mask; the pattern keeps it to the junctions it was measured on.)"""
+    g = gm.graph
+    forks = 0
+    order = [n for n in g.nodes if n.op == "call_module"]
+    for node in list(order):
+        if type(mods.get(node.target)) is not AddBiasReLU:
+            continue
+        users = list(node.users)
+        if len(users) != 2 or mods[node.target].link_out is not None:
+            continue
+        if any(u.op != "call_module" or type(mods.get(u.target)) is AddBiasReLU for u in users):
+            continue
+        if any(sum(a is node for a in u.all_input_nodes) != 1 or u.kwargs for u in users):
+            continue
+        # the nearest junction: the first AddBiasReLU (graph order is topological) that either branch
+        # reaches has to take one branch per operand
+        below = [_descendants(u) for u in users]
+        join = next((j for j in order[order.index(node) + 1:]
+                     if type(mods.get(j.target)) is AddBiasReLU and (j in below[0] or j in below[1])), None)
+        if join is None or len(join.args) != 2 or not all(isinstance(a, fx.Node) for a in join.args):
+            continue
+        a, b = join.args
+        if not ((a in below[0] and b in below[1]) or (a in below[1] and b in below[0])):
+            continue
+        link = _SkipLink()
+        fork = GradFork()
+        fork.src = link
+        mods[node.target].fork_out = link
+        name = add_mod("grad_fork", fork)
+        with g.inserting_after(node):
+            f = g.call_module(name, (node,))
+        with g.inserting_after(f):
+            outs = [g.call_function(operator.getitem, (f, i)) for i in (1, 0)][::-1]
+        for u, o in zip(users, outs):
+            u.replace_input_with(node, o)
+        forks += 1
+    return forks

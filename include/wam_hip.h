@@ -291,6 +291,36 @@ int wam_accumulate_f32(int64_t groups, int64_t len, const float* src, float scal
 int wam_trapz_f32(int64_t groups, int64_t k0, int64_t len, const float* src, const float* weights,
                   float* prev_f32, float* acc_f32, double* prev_f64, double* acc_f64, void* stream);
 
+/* Second moments of the SmoothGrad samples (SmoothGrad-squared, VarGrad). With v the float32 value
+ * the matching sum entry adds at an element for sample s (formed by the same operations), every
+ * entry below updates, for s in [0, groups) in order,
+ *   sum += fp64(v),  sumsq += fp64(v) * fp64(v)     (the product is exact in float64)
+ * reading each map value once. sum / sumsq are float64, laid out like the sum entry's accumulator,
+ * owned and zeroed by the caller; launches chain (groups 3 then 2 give the bits of one launch of 5).
+ * wam_frame_moments(_coef): v of wam_frame_accumulate(_coef), same arguments; sum comes out
+ * bit-identical to the frame those entries write, and the two orders give equal bits.
+ * wam_cube_moments: v of wam_cube_accumulate (the gathered |g| voxel, 0 where src[p] = -1), plain
+ * weights of 1 (not the legacy running average).
+ * wam_moments_f32: v = src[s*len + e], element-wise. */
+int wam_frame_moments(int64_t groups, int64_t group_items, int64_t frame_len, const int32_t* src,
+                      const int32_t* band, const float* maps, int64_t maps_item_len, const float* band_max,
+                      int n_bands, int normalize, double* sum, double* sumsq, void* stream);
+int wam_frame_moments_coef(int64_t groups, int64_t group_items, int64_t maps_item_len, int64_t frame_len,
+                           const int32_t* dst, const int32_t* cband, const float* maps, const float* band_max,
+                           int n_bands, int normalize, double* sum, double* sumsq, void* stream);
+int wam_cube_moments(int64_t groups, int64_t group_items, int64_t cube_len, const int32_t* src,
+                     const float* maps, int64_t maps_item_len, double* sum, double* sumsq, void* stream);
+int wam_moments_f32(int64_t groups, int64_t len, const float* src, double* sum, double* sumsq, void* stream);
+
+/* (sum, sumsq) over n >= 1 samples -> out[e], in float64:
+ *   kind 0: sum / n                                      (the SmoothGrad mean; sumsq may be NULL)
+ *   kind 1: sumsq / n                                    (SmoothGrad-squared; sum may be NULL)
+ *   kind 2: max(fma(-m, m, sumsq / n), 0), m = sum / n   (VarGrad: the population variance; NaN
+ *           propagates, n = 1 gives exactly 0)
+ * written to exactly one of out_f64 / out_f32 (the float64 result rounded once). */
+int wam_moments_finish(int64_t len, const double* sum, const double* sumsq, int64_t n, int kind,
+                       double* out_f64, float* out_f32, void* stream);
+
 /* .scales side output (lib/wam_2D.py:488-536 reproject_wam): for each item and level j,
  * out[item, j] = sum over the H, V, D quadrants of bilinear (cv2 INTER_LINEAR, half-pixel)
  * upsampling to size x size; with approx, out[item, J] = upsampled approximation corner. The

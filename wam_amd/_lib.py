@@ -65,6 +65,12 @@ _SIGS = {
                                     c_vp]),
     "wam_accumulate_f32": (c_int, [c_i64, c_i64, c_vp, c_f32, c_vp, c_vp]),
     "wam_trapz_f32": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wam_frame_moments": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    "wam_frame_moments_coef": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp,
+                                       c_vp]),
+    "wam_cube_moments": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wam_moments_f32": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wam_moments_finish": (c_int, [c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     "wam_reproject_scales": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "wam_disentangle_scales": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "wam_plan_caps": (c_int, [c_vp]),

@@ -365,45 +365,86 @@ __device__ __forceinline__ void cube_step(float& a, float& pv, float v, int mode
 }
 
 // ------------------------------------------------------------------------------ frame accumulate
-__global__ void __launch_bounds__(256) k_frame_accumulate(int64_t groups, int64_t group_items, int64_t frame_len,
-                                                          const int32_t* __restrict__ src,
-                                                          const int32_t* __restrict__ band,
-                                                          const float* __restrict__ maps, int64_t maps_item_len,
-                                                          const float* __restrict__ band_max, int n_bands,
-                                                          int normalize, double* __restrict__ frame) {
+// One second-moment step on the float64 pair (S, Q): S += v, Q += v * v. The product of two widened
+// float32 values is exact in float64, so Q carries summation rounding only (and a contraction of
+// the product and the add into one fma gives the same bits).
+__device__ __forceinline__ void moment_step(double& s, double& q, float v) {
+  const double d = (double)v;
+  s += d;
+  q += d * d;
+}
+
+// Element bodies of the two mosaic orders, shared by the SmoothGrad sum (MOMENTS false: frame alone)
+// and the moment kernels (MOMENTS true: frame = S, frame_q = Q; S takes the very steps of the sum).
+template <bool MOMENTS>
+__device__ __forceinline__ void frame_accumulate_pixels(int64_t groups, int64_t group_items, int64_t frame_len,
+                                                        const int32_t* __restrict__ src,
+                                                        const int32_t* __restrict__ band,
+                                                        const float* __restrict__ maps, int64_t maps_item_len,
+                                                        const float* __restrict__ band_max, int n_bands,
+                                                        int normalize, double* __restrict__ frame,
+                                                        double* __restrict__ frame_q, int64_t t0, int64_t tstep) {
   const int64_t total = group_items * frame_len;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t t = t0; t < total; t += tstep) {
     const int64_t p = t % frame_len;
     const int64_t n = t / frame_len;
     const int32_t sidx = src[p];
     if (sidx < 0) continue;
     const int32_t b = band[p];
     double acc = frame[t];
+    [[maybe_unused]] double q = 0.0;
+    if constexpr (MOMENTS) q = frame_q[t];
     for_samples(groups, maps + n * maps_item_len + sidx, group_items * maps_item_len, band_max, n_bands, b, normalize,
-                [&](int64_t, float v, float m) { acc += (double)(normalize ? v / m : v); });
+                [&](int64_t, float v, float m) {
+                  if constexpr (MOMENTS) moment_step(acc, q, normalize ? v / m : v);
+                  else acc += (double)(normalize ? v / m : v);
+                });
     frame[t] = acc;
+    if constexpr (MOMENTS) frame_q[t] = q;
   }
+}
+
+__global__ void __launch_bounds__(256) k_frame_accumulate(int64_t groups, int64_t group_items, int64_t frame_len,
+                                                          const int32_t* __restrict__ src,
+                                                          const int32_t* __restrict__ band,
+                                                          const float* __restrict__ maps, int64_t maps_item_len,
+                                                          const float* __restrict__ band_max, int n_bands,
+                                                          int normalize, double* __restrict__ frame) {
+  frame_accumulate_pixels<false>(groups, group_items, frame_len, src, band, maps, maps_item_len, band_max, n_bands,
+                                 normalize, frame, nullptr, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+      (int64_t)gridDim.x * blockDim.x);
+}
+
+// both moments of the mosaic pixel in one pass over the maps (wam_frame_moments)
+__global__ void __launch_bounds__(256) k_frame_moments(int64_t groups, int64_t group_items, int64_t frame_len,
+                                                       const int32_t* __restrict__ src,
+                                                       const int32_t* __restrict__ band,
+                                                       const float* __restrict__ maps, int64_t maps_item_len,
+                                                       const float* __restrict__ band_max, int n_bands, int normalize,
+                                                       double* __restrict__ sum, double* __restrict__ sumsq) {
+  frame_accumulate_pixels<true>(groups, group_items, frame_len, src, band, maps, maps_item_len, band_max, n_bands,
+                                normalize, sum, sumsq, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+      (int64_t)gridDim.x * blockDim.x);
 }
 
 // the same accumulation in COEFFICIENT order (dst = frame pixel of coefficient k or -1; the mosaic
 // is injective): the maps are read as contiguous rows (whole cache lines) and only the fp64 frame
 // is addressed through the mosaic, so the partial lines at band-row edges fall on the 16-B/pixel
 // frame instead of the per-sample map reads. Per pixel the sum order is unchanged (bit-identical).
-__global__ void __launch_bounds__(256) k_frame_accumulate_coef(int64_t groups, int64_t group_items,
-                                                               int64_t maps_item_len, int64_t frame_len,
-                                                               const int32_t* __restrict__ dst,
-                                                               const int32_t* __restrict__ cband,
-                                                               const float* __restrict__ maps,
-                                                               const float* __restrict__ band_max, int n_bands,
-                                                               int normalize, int64_t items_per_thread,
-                                                               double* __restrict__ frame) {
+template <bool MOMENTS>
+__device__ __forceinline__ void frame_accumulate_coefs(int64_t groups, int64_t group_items, int64_t maps_item_len,
+                                                       int64_t frame_len, const int32_t* __restrict__ dst,
+                                                       const int32_t* __restrict__ cband,
+                                                       const float* __restrict__ maps,
+                                                       const float* __restrict__ band_max, int n_bands, int normalize,
+                                                       int64_t items_per_thread, double* __restrict__ frame,
+                                                       double* __restrict__ frame_q, int64_t t0, int64_t tstep) {
   // thread per (coefficient k, run of items_per_thread items): the mosaic tables (8 B per
   // coefficient, several MB at 512^2, beyond an XCD's L2) are read once per run of items instead of
   // once per item
   const int64_t mstride = group_items * maps_item_len;
   const int64_t runs = (group_items + items_per_thread - 1) / items_per_thread;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < runs * maps_item_len;
-       t += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t t = t0; t < runs * maps_item_len; t += tstep) {
     const int64_t r = t / maps_item_len;
     const int64_t k = t - r * maps_item_len;
     const int32_t d = dst[k];
@@ -413,11 +454,44 @@ __global__ void __launch_bounds__(256) k_frame_accumulate_coef(int64_t groups, i
     for (int64_t n = r * items_per_thread; n < n1; ++n) {
       double* fp = frame + n * frame_len + d;
       double acc = *fp;
+      [[maybe_unused]] double q = 0.0;
+      if constexpr (MOMENTS) q = frame_q[n * frame_len + d];
       for_samples(groups, maps + n * maps_item_len + k, mstride, band_max, n_bands, b, normalize,
-                  [&](int64_t, float v, float m) { acc += (double)(normalize ? v / m : v); });
+                  [&](int64_t, float v, float m) {
+                    if constexpr (MOMENTS) moment_step(acc, q, normalize ? v / m : v);
+                    else acc += (double)(normalize ? v / m : v);
+                  });
       *fp = acc;
+      if constexpr (MOMENTS) frame_q[n * frame_len + d] = q;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) k_frame_accumulate_coef(int64_t groups, int64_t group_items,
+                                                               int64_t maps_item_len, int64_t frame_len,
+                                                               const int32_t* __restrict__ dst,
+                                                               const int32_t* __restrict__ cband,
+                                                               const float* __restrict__ maps,
+                                                               const float* __restrict__ band_max, int n_bands,
+                                                               int normalize, int64_t items_per_thread,
+                                                               double* __restrict__ frame) {
+  frame_accumulate_coefs<false>(groups, group_items, maps_item_len, frame_len, dst, cband, maps, band_max, n_bands,
+                                normalize, items_per_thread, frame, nullptr, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+      (int64_t)gridDim.x * blockDim.x);
+}
+
+// both moments in coefficient order (wam_frame_moments_coef): per pixel the steps of k_frame_moments
+__global__ void __launch_bounds__(256) k_frame_moments_coef(int64_t groups, int64_t group_items,
+                                                            int64_t maps_item_len, int64_t frame_len,
+                                                            const int32_t* __restrict__ dst,
+                                                            const int32_t* __restrict__ cband,
+                                                            const float* __restrict__ maps,
+                                                            const float* __restrict__ band_max, int n_bands,
+                                                            int normalize, int64_t items_per_thread,
+                                                            double* __restrict__ sum, double* __restrict__ sumsq) {
+  frame_accumulate_coefs<true>(groups, group_items, maps_item_len, frame_len, dst, cband, maps, band_max, n_bands,
+                               normalize, items_per_thread, sum, sumsq, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+      (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void __launch_bounds__(256) k_frame_trapz(int64_t groups, int64_t k0, int64_t group_items, int64_t frame_len,
@@ -499,6 +573,11 @@ double frame_bytes(int64_t groups, int64_t group_items, int64_t frame_len) {
   return 4.0 * (double)groups * group_items * frame_len + 16.0 * group_items * frame_len + 8.0 * frame_len;
 }
 
+// the moment kernels': the maps once, both accumulators read and written
+double frame_moments_bytes(int64_t groups, int64_t group_items, int64_t frame_len) {
+  return frame_bytes(groups, group_items, frame_len) + 16.0 * group_items * frame_len;
+}
+
 // Coefficient order: mosaic tables beyond ~2 MB (8 B per coefficient; 512^2 planes) would be
 // re-read from HBM per item, so each thread then takes a run of items of one coefficient, the runs
 // sized for about target_threads threads; small tables stay in L2 and every (item, coefficient)
@@ -539,6 +618,39 @@ __global__ void __launch_bounds__(256) k_cube_accumulate(int64_t groups, int64_t
 // each load instruction covers 64 consecutive voxels (the gathers follow the mosaic's runs of
 // consecutive coefficients); otherwise four consecutive voxels per thread with 16-byte index /
 // accumulator accesses (cube_len % 4 == 0, 16-byte aligned).
+// The two pieces the four-voxel kernels (accumulate, moments) share: the voxels of unit t4, and the
+// sample loop over them -- f(s, e, value of voxel e in sample s, 0 outside the mosaic) for
+// s = 0 .. groups - 1 in order, up to 4 samples' gathers in flight per voxel.
+template <bool STRIDED>
+__device__ __forceinline__ void cube_voxels4(int64_t t4, int lane, int64_t (&tv)[4]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) tv[e] = STRIDED ? 4 * (t4 - lane) + lane + 64 * e : 4 * t4 + e;
+}
+
+template <class F>
+__device__ __forceinline__ void for_cube_samples4(int64_t groups, int64_t group_items, int64_t cube_len,
+                                                  const int64_t (&tv)[4], const int (&sv)[4],
+                                                  const float* __restrict__ maps, int64_t maps_item_len, F f) {
+  int64_t nv[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) nv[e] = tv[e] / cube_len;
+  for (int64_t s = 0; s < groups; s += 4) {
+    float v[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t su = s + u < groups ? s + u : s;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[u][e] = maps[(su * group_items + nv[e]) * maps_item_len + (sv[e] >= 0 ? sv[e] : 0)];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (s + u >= groups) break;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f(s + u, e, sv[e] >= 0 ? v[u][e] : 0.f);
+    }
+  }
+}
+
 template <bool STRIDED>
 __global__ void __launch_bounds__(256) k_cube_accumulate4(int64_t groups, int64_t k0, int64_t group_items,
                                                           int64_t cube_len, const int32_t* __restrict__ src,
@@ -549,8 +661,7 @@ __global__ void __launch_bounds__(256) k_cube_accumulate4(int64_t groups, int64_
   const int lane = threadIdx.x & 63;
   for (int64_t t4 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t4 < total4; t4 += (int64_t)gridDim.x * blockDim.x) {
     int64_t tv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) tv[e] = STRIDED ? 4 * (t4 - lane) + lane + 64 * e : 4 * t4 + e;
+    cube_voxels4<STRIDED>(t4, lane, tv);
     int sv[4];
     float a[4], pv[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (STRIDED) {
@@ -570,25 +681,8 @@ __global__ void __launch_bounds__(256) k_cube_accumulate4(int64_t groups, int64_
         pv[0] = p4.x, pv[1] = p4.y, pv[2] = p4.z, pv[3] = p4.w;
       }
     }
-    int64_t nv[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) nv[e] = tv[e] / cube_len;
-    for (int64_t s = 0; s < groups; s += 4) {  // up to 4 samples' gathers in flight per voxel
-      float v[4][4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t su = s + u < groups ? s + u : s;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[u][e] = maps[(su * group_items + nv[e]) * maps_item_len + (sv[e] >= 0 ? sv[e] : 0)];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (s + u >= groups) break;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          cube_step(a[e], pv[e], sv[e] >= 0 ? v[u][e] : 0.f, mode, n_total, weights, s + u, k0);
-      }
-    }
+    for_cube_samples4(groups, group_items, cube_len, tv, sv, maps, maps_item_len,
+                      [&](int64_t s, int e, float v) { cube_step(a[e], pv[e], v, mode, n_total, weights, s, k0); });
     if constexpr (STRIDED) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -599,6 +693,107 @@ __global__ void __launch_bounds__(256) k_cube_accumulate4(int64_t groups, int64_
       *reinterpret_cast<float4*>(acc + tv[0]) = make_float4(a[0], a[1], a[2], a[3]);
       if (prev) *reinterpret_cast<float4*>(prev + tv[0]) = make_float4(pv[0], pv[1], pv[2], pv[3]);
     }
+  }
+}
+
+// both moments of the |g| cube voxel (wam_cube_moments), plain weights of 1, float64 accumulators.
+// FORM 2 / 1: the strided / consecutive four-voxel forms of k_cube_accumulate4 (the consecutive one
+// with 16-byte index and accumulator accesses); FORM 0: one voxel per thread, any length and
+// alignment. A voxel outside the mosaic takes steps of 0, as in k_cube_accumulate.
+template <int FORM>
+__global__ void __launch_bounds__(256) k_cube_moments(int64_t groups, int64_t group_items, int64_t cube_len,
+                                                      const int32_t* __restrict__ src,
+                                                      const float* __restrict__ maps, int64_t maps_item_len,
+                                                      double* __restrict__ sum, double* __restrict__ sumsq) {
+  if constexpr (FORM == 0) {
+    const int64_t total = group_items * cube_len;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t p = t % cube_len;
+      const int64_t n = t / cube_len;
+      const int32_t sidx = src[p];
+      double a = sum[t], q = sumsq[t];
+      for (int64_t s = 0; s < groups; ++s)
+        moment_step(a, q, sidx >= 0 ? maps[(s * group_items + n) * maps_item_len + sidx] : 0.f);
+      sum[t] = a;
+      sumsq[t] = q;
+    }
+  } else {
+    constexpr bool STRIDED = FORM == 2;
+    const int64_t total4 = group_items * cube_len / 4;  // 4-voxel units (cube_len % 4 == 0)
+    const int lane = threadIdx.x & 63;
+    for (int64_t t4 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t4 < total4;
+         t4 += (int64_t)gridDim.x * blockDim.x) {
+      int64_t tv[4];
+      cube_voxels4<STRIDED>(t4, lane, tv);
+      int sv[4];
+      double a[4], q[4];
+      if constexpr (STRIDED) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          sv[e] = src[tv[e] % cube_len];
+          a[e] = sum[tv[e]];
+          q[e] = sumsq[tv[e]];
+        }
+      } else {
+        const int4 si = *reinterpret_cast<const int4*>(src + tv[0] % cube_len);
+        sv[0] = si.x, sv[1] = si.y, sv[2] = si.z, sv[3] = si.w;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const double2 a2 = *reinterpret_cast<const double2*>(sum + tv[0] + 2 * h);
+          const double2 q2 = *reinterpret_cast<const double2*>(sumsq + tv[0] + 2 * h);
+          a[2 * h] = a2.x, a[2 * h + 1] = a2.y, q[2 * h] = q2.x, q[2 * h + 1] = q2.y;
+        }
+      }
+      for_cube_samples4(groups, group_items, cube_len, tv, sv, maps, maps_item_len,
+                        [&](int64_t, int e, float v) { moment_step(a[e], q[e], v); });
+      if constexpr (STRIDED) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          sum[tv[e]] = a[e];
+          sumsq[tv[e]] = q[e];
+        }
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          *reinterpret_cast<double2*>(sum + tv[0] + 2 * h) = make_double2(a[2 * h], a[2 * h + 1]);
+          *reinterpret_cast<double2*>(sumsq + tv[0] + 2 * h) = make_double2(q[2 * h], q[2 * h + 1]);
+        }
+      }
+    }
+  }
+}
+
+// both moments of a generic fp32 stream (1D melspec / coefficient gradients): element-wise over
+// `groups` samples in order
+__global__ void __launch_bounds__(256) k_moments_f32(int64_t groups, int64_t len, const float* __restrict__ src,
+                                                     double* __restrict__ sum, double* __restrict__ sumsq) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < len; e += (int64_t)gridDim.x * blockDim.x) {
+    double a = sum[e], q = sumsq[e];
+    for (int64_t s = 0; s < groups; ++s) moment_step(a, q, src[s * len + e]);
+    sum[e] = a;
+    sumsq[e] = q;
+  }
+}
+
+// (S, Q, n) -> kind 0 the mean S / n, 1 the mean square Q / n, 2 the population variance
+// max(fma(-m, m, Q / n), 0) with m = S / n (NaN propagates; n = 1: fma(-v, v, v * v) = 0 exactly).
+// out64 or out32 (the float64 result rounded once).
+__global__ void __launch_bounds__(256) k_moments_finish(int64_t len, const double* __restrict__ sum,
+                                                        const double* __restrict__ sumsq, double n, int kind,
+                                                        double* __restrict__ out64, float* __restrict__ out32) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < len; e += (int64_t)gridDim.x * blockDim.x) {
+    double r;
+    if (kind == 0) {
+      r = sum[e] / n;
+    } else if (kind == 1) {
+      r = sumsq[e] / n;
+    } else {
+      const double m = sum[e] / n;
+      r = fma(-m, m, sumsq[e] / n);
+      r = (r != r || r > 0.0) ? r : 0.0;
+    }
+    if (out64) out64[e] = r;
+    else out32[e] = (float)r;
   }
 }
 
@@ -974,6 +1169,81 @@ int wam_trapz_f32(int64_t groups, int64_t k0, int64_t len, const float* src, con
               4.0 * (double)groups * len + (acc_f64 ? 16.0 : 8.0) * (double)len * (weights ? 1.0 : 2.0));
   hipLaunchKernelGGL(k_trapz_f32, dim3(wam_grid(len, 256)), dim3(256), 0, (hipStream_t)stream, groups, k0, len, src,
                      weights, prev_f32, acc_f32, prev_f64, acc_f64);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+// ---- second moments (SmoothGrad-squared / VarGrad): S and Q in one pass over the maps
+int wam_frame_moments(int64_t groups, int64_t group_items, int64_t frame_len, const int32_t* src, const int32_t* band,
+                      const float* maps, int64_t maps_item_len, const float* band_max, int n_bands, int normalize,
+                      double* sum, double* sumsq, void* stream) {
+  if (!frame_args_ok(groups, group_items, frame_len, frame_len, src && band && maps && sum && sumsq, normalize,
+                     band_max))
+    return WAM_ERR_INVALID_ARG;
+  const int64_t work = group_items * frame_len;
+  if (work == 0 || groups == 0) return WAM_OK;
+  WamTimer tm((hipStream_t)stream, "k_frame_moments", frame_moments_bytes(groups, group_items, frame_len));
+  hipLaunchKernelGGL(k_frame_moments, dim3(wam_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, groups,
+                     group_items, frame_len, src, band, maps, maps_item_len, band_max, n_bands, normalize, sum, sumsq);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int wam_frame_moments_coef(int64_t groups, int64_t group_items, int64_t maps_item_len, int64_t frame_len,
+                           const int32_t* dst, const int32_t* cband, const float* maps, const float* band_max,
+                           int n_bands, int normalize, double* sum, double* sumsq, void* stream) {
+  if (!frame_args_ok(groups, group_items, maps_item_len, frame_len, dst && cband && maps && sum && sumsq, normalize,
+                     band_max))
+    return WAM_ERR_INVALID_ARG;
+  const int64_t work = group_items * maps_item_len;
+  if (work == 0 || groups == 0) return WAM_OK;
+  WamTimer tm((hipStream_t)stream, "k_frame_moments_coef", frame_moments_bytes(groups, group_items, frame_len));
+  const int64_t ipt = coef_items_per_thread(maps_item_len, group_items, work, int64_t(1) << 20);
+  const int64_t threads = (group_items + ipt - 1) / ipt * maps_item_len;
+  hipLaunchKernelGGL(k_frame_moments_coef, dim3(wam_grid(threads, 256)), dim3(256), 0, (hipStream_t)stream, groups,
+                     group_items, maps_item_len, frame_len, dst, cband, maps, band_max, n_bands, normalize, ipt, sum,
+                     sumsq);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int wam_cube_moments(int64_t groups, int64_t group_items, int64_t cube_len, const int32_t* src, const float* maps,
+                     int64_t maps_item_len, double* sum, double* sumsq, void* stream) {
+  if (groups < 0 || group_items < 0 || cube_len < 0 || maps_item_len < 0 || !src || !maps || !sum || !sumsq)
+    return WAM_ERR_INVALID_ARG;
+  const int64_t work = group_items * cube_len;
+  if (work == 0 || groups == 0) return WAM_OK;
+  // algorithmic bytes: the gathered maps once per (sample, voxel), both accumulators read and
+  // written, the index map once
+  WamTimer tm((hipStream_t)stream, "k_cube_moments", 4.0 * (double)groups * work + 32.0 * work + 4.0 * cube_len);
+  // the choice of wam_cube_accumulate
+  const bool vec4 = cube_len % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)sum & 15) == 0 &&
+                    ((uintptr_t)sumsq & 15) == 0;
+  auto k = !vec4 ? k_cube_moments<0> : work % 256 == 0 ? k_cube_moments<2> : k_cube_moments<1>;
+  hipLaunchKernelGGL(k, dim3(wam_grid(vec4 ? work / 4 : work, 256)), dim3(256), 0, (hipStream_t)stream, groups,
+                     group_items, cube_len, src, maps, maps_item_len, sum, sumsq);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int wam_moments_f32(int64_t groups, int64_t len, const float* src, double* sum, double* sumsq, void* stream) {
+  if (groups < 0 || len < 0 || !src || !sum || !sumsq) return WAM_ERR_INVALID_ARG;
+  if (len == 0 || groups == 0) return WAM_OK;
+  WamTimer tm((hipStream_t)stream, "k_moments_f32", 4.0 * (double)groups * len + 32.0 * (double)len);
+  hipLaunchKernelGGL(k_moments_f32, dim3(wam_grid(len, 256)), dim3(256), 0, (hipStream_t)stream, groups, len, src, sum,
+                     sumsq);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+int wam_moments_finish(int64_t len, const double* sum, const double* sumsq, int64_t n, int kind, double* out_f64,
+                       float* out_f32, void* stream) {
+  if (len < 0 || n < 1 || kind < 0 || kind > 2 || (!out_f64 == !out_f32)) return WAM_ERR_INVALID_ARG;
+  if ((kind != 1 && !sum) || (kind != 0 && !sumsq)) return WAM_ERR_INVALID_ARG;
+  if (len == 0) return WAM_OK;
+  WamTimer tm((hipStream_t)stream, "k_moments_finish", ((kind == 2 ? 16.0 : 8.0) + (out_f64 ? 8.0 : 4.0)) * (double)len);
+  hipLaunchKernelGGL(k_moments_finish, dim3(wam_grid(len, 256)), dim3(256), 0, (hipStream_t)stream, len, sum, sumsq,
+                     (double)n, kind, out_f64, out_f32);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

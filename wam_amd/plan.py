@@ -472,6 +472,44 @@ def trapz_stream(src, groups, k0, prev, acc, weights=None):
                                 stream_of(acc.device)))
 
 
+# second moments of the SmoothGrad samples: S (sum) and Q (sum of squares), float64, zeroed by the caller
+def frame_moments(groups, group_items, gmap, maps, maps_item_len, band_max, n_bands, normalize, sum_, sumsq):
+    """frame_accumulate's sum and the sum of squares of the same values, one pass over the maps."""
+    src, band = gmap
+    inv = _inverse_map(gmap, maps_item_len)
+    if inv is not None:  # coefficient order: contiguous map reads
+        check(lib.wam_frame_moments_coef(groups, group_items, maps_item_len, src.numel(), ptr(inv[0]), ptr(inv[1]),
+                                         ptr(maps), ptr(band_max), n_bands, int(bool(normalize)), ptr(sum_),
+                                         ptr(sumsq), stream_of(sum_.device)))
+        return
+    check(lib.wam_frame_moments(groups, group_items, src.numel(), ptr(src), ptr(band), ptr(maps), maps_item_len,
+                                ptr(band_max), n_bands, int(bool(normalize)), ptr(sum_), ptr(sumsq),
+                                stream_of(sum_.device)))
+
+
+def cube_moments(groups, group_items, src, maps, maps_item_len, sum_, sumsq):
+    check(lib.wam_cube_moments(groups, group_items, src.numel(), ptr(src), ptr(maps), maps_item_len, ptr(sum_),
+                               ptr(sumsq), stream_of(sum_.device)))
+
+
+def moments_f32(src, groups, sum_, sumsq):
+    check(lib.wam_moments_f32(groups, sum_.numel(), ptr(src), ptr(sum_), ptr(sumsq), stream_of(sum_.device)))
+
+
+MOMENT_KINDS = {"mean": 0, "smooth_sq": 1, "vargrad": 2}
+
+
+def moments_finish(sum_, sumsq, n, kind, dtype=torch.float64):
+    """(S, Q) over n samples -> S / n ('mean'), Q / n ('smooth_sq') or the population variance
+    max(fma(-m, m, Q / n), 0), m = S / n ('vargrad'), as a float64 or float32 tensor of S's shape."""
+    sum_, sumsq = sum_.contiguous(), sumsq.contiguous()
+    out = torch.empty(sum_.shape, dtype=dtype, device=sum_.device)
+    o64, o32 = (out, None) if dtype == torch.float64 else (None, out)
+    check(lib.wam_moments_finish(sum_.numel(), ptr(sum_), ptr(sumsq), int(n), MOMENT_KINDS[kind], ptr(o64), ptr(o32),
+                                 stream_of(sum_.device)))
+    return out
+
+
 def reproject_scales(avg, levels, approx):
     """avg: [items, size, size] float64 cuda -> [items, levels(+1), size, size] float64."""
     items, size = avg.shape[0], avg.shape[1]

@@ -15,7 +15,8 @@ from .engine import (Shard, auto_group, chunks, ig_weights, input_gradient, Lega
                      param_grad_sum, require_gpu_device, trainable_params)
 from .melspec import kernel_supported, mel_adjoint, mel_forward, melspec_db
 from .profiling import phase
-from .plan import CAP_NOISY_WAVEDEC, accumulate_f32, get_plan, item_sigma, noise_add, trapz_stream
+from .plan import (CAP_NOISY_WAVEDEC, accumulate_f32, get_plan, item_sigma, moments_f32, moments_finish, noise_add,
+                   trapz_stream)
 
 
 def normalize(data):
@@ -198,11 +199,16 @@ class WaveletAttribution1D(BaseWAM1D):
         self.noise = noise
         self.sample_batch = sample_batch
         self.dist = dist
+        self.smooth_mean = None  # (melspec, [bands]) mean of the last 'smooth_sq' / 'vargrad' call
         self.wam = BaseWAM1D(model, wavelet=wavelet, J=J, mode=mode, device=device, approx_coeffs=approx_coeffs,
                              n_mels=n_mels, n_fft=n_fft, sample_rate=sample_rate, autocast_dtype=autocast_dtype)
 
-    def smooth_wam(self, x, y):
-        """lib/wam_1D.py:294-343: mean over noisy samples of the raw gradients."""
+    def smooth_wam(self, x, y, moment=None):
+        """lib/wam_1D.py:294-343: mean over noisy samples of the raw gradients. moment (build-only):
+        'smooth_sq' / 'vargrad' = the mean square / the population variance of those per-sample raw
+        gradients instead (wam_moments_f32: sum and sum of squares in float64, one pass over the
+        gradients; float32 results), with the mean of that run left in self.smooth_mean as
+        (melspec, [bands])."""
         dev = self._dev
         if isinstance(x, list):
             x = _peak_normalise(x)
@@ -219,8 +225,10 @@ class WaveletAttribution1D(BaseWAM1D):
         # accumulators exist before the loop: a rank whose sample range is empty (n_samples <
         # world size) still joins the all-reduce with zeros
         self._mel_shape = (n, 1, plan.rec_shape[0] // (self.n_fft // 2) + 1, self.n_mels)
-        mel_acc = torch.zeros(int(np.prod(self._mel_shape)), dtype=torch.float32, device=dev)
-        c_acc = torch.zeros(n * plan.coeff_numel, dtype=torch.float32, device=dev)
+        acc_dtype = torch.float32 if moment is None else torch.float64
+        mel_acc = torch.zeros(int(np.prod(self._mel_shape)), dtype=acc_dtype, device=dev)
+        c_acc = torch.zeros(n * plan.coeff_numel, dtype=acc_dtype, device=dev)
+        mel_q, c_q = (None, None) if moment is None else (torch.zeros_like(mel_acc), torch.zeros_like(c_acc))
         with param_grad_sum(trainable_params(self.model), shard):
             for s0, cnt in chunks(s_lo, s_hi, group):
                 with phase("noise+wavedec"):
@@ -236,21 +244,38 @@ class WaveletAttribution1D(BaseWAM1D):
                 if g_mel.numel() != cnt * mel_acc.numel():
                     raise RuntimeError("melspec gradient shape %s does not match %s" % (tuple(g_mel.shape),
                                                                                          self._mel_shape))
-                accumulate_f32(g_mel, cnt, mel_acc)
+                if moment is None:
+                    accumulate_f32(g_mel, cnt, mel_acc)
+                else:
+                    moments_f32(g_mel, cnt, mel_acc, mel_q)
                 for b in range(plan.nbands):
                     nb = int(np.prod(plan.band_shapes[b]))
+                    lo, hi = n * plan.band_offsets[b], n * (plan.band_offsets[b] + nb)
                     src = cg[cnt * n * plan.band_offsets[b]:cnt * n * (plan.band_offsets[b] + nb)]
-                    accumulate_f32(src, cnt, c_acc[n * plan.band_offsets[b]:n * (plan.band_offsets[b] + nb)])
+                    if moment is None:
+                        accumulate_f32(src, cnt, c_acc[lo:hi])
+                    else:
+                        moments_f32(src, cnt, c_acc[lo:hi], c_q[lo:hi])
                 self.wam._record(plan, flat, cnt * n, (cnt - 1) * n, cg, cnt * n, (cnt - 1) * n, n)
         if legacy is not None:
             legacy.finish()
         with phase("collectives"):
-            shard.all_reduce_sum(mel_acc)
-            shard.all_reduce_sum(c_acc)
-        accumulate_f32(mel_acc, 0, mel_acc, scale=float(self.n_samples))
-        accumulate_f32(c_acc, 0, c_acc, scale=float(self.n_samples))
-        mel = mel_acc.view(self._mel_shape).cpu().numpy().squeeze()
-        avg = [v.cpu().numpy() for v in plan.split(c_acc, n)]
+            for acc in (mel_acc, c_acc, mel_q, c_q):  # the sums of squares are linear too
+                if acc is not None:
+                    shard.all_reduce_sum(acc)
+        def host(m, c):
+            return m.view(self._mel_shape).cpu().numpy().squeeze(), [v.cpu().numpy() for v in plan.split(c, n)]
+
+        def finish(kind):
+            return host(moments_finish(mel_acc, mel_q, self.n_samples, kind, torch.float32),
+                        moments_finish(c_acc, c_q, self.n_samples, kind, torch.float32))
+        if moment is None:
+            accumulate_f32(mel_acc, 0, mel_acc, scale=float(self.n_samples))
+            accumulate_f32(c_acc, 0, c_acc, scale=float(self.n_samples))
+            mel, avg = host(mel_acc, c_acc)
+        else:
+            self.smooth_mean = finish("mean")
+            mel, avg = finish(moment)
         self.melspecs = mel
         self.grad_coeffs = avg
         return mel, avg
@@ -303,6 +328,8 @@ class WaveletAttribution1D(BaseWAM1D):
             return self.smooth_wam(x, y)
         elif self.method == "integratedgrad":
             return self.integrated_wam(x, y)
+        elif self.method in ("smooth_sq", "vargrad"):
+            return self.smooth_wam(x, y, moment=self.method)
 
 
 class VisualizerWAM1D(WaveletAttribution1D):

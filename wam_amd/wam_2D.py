@@ -7,6 +7,11 @@ scaling, the per-subband channel-mean |.| with batch-global maxima and the mosai
 run as HIP kernels (libwam_hip.so) on the model's GPU; several noise samples / IG steps are
 batched into one model forward/backward; nothing goes back to the host but the final map.
 
+Methods beyond the reference's 'smooth' and 'integratedgrad': 'smooth_sq' (the mean of the squared
+per-sample SmoothGrad map) and 'vargrad' (its population variance over the noise samples), from a
+sum and a sum of squares kept in float64 by one epilogue pass (wam_frame_moments); the plain mean of
+the same run is left in ``smooth_mean``. Any other method name returns None, as in the reference.
+
 Build-only keyword arguments (all optional, after the reference's own):
   noise          'numpy' (default) = the reference's legacy np.random stream, bit-identical noise;
                  'philox' = counter-based Philox4x32-10 generated on the GPU (fast path).
@@ -39,8 +44,9 @@ from .profiling import phase
 from .constants import WaveletDetailTuple2d
 from .engine import (GradModel, LegacyNoise, Shard, auto_group, chunks, ig_weights, model_device, param_grad_sum,
                      require_gpu_device, wam_budget_bytes, wam_group)
-from .plan import (CAP_ADJOINT_MAPS, CAP_BF16_NHWC, CAP_NOISY_WAVEDEC, disentangle_scales, frame_accumulate, frame_trapz,
-                   get_plan, item_sigma, noise_add, reproject_scales, subband_maps)
+from .plan import (CAP_ADJOINT_MAPS, CAP_BF16_NHWC, CAP_NOISY_WAVEDEC, disentangle_scales, frame_accumulate,
+                   frame_moments, frame_trapz, get_plan, item_sigma, moments_finish, noise_add, reproject_scales,
+                   subband_maps)
 
 
 def _to_numpy_2d(plan, flat, batch_items, n, c, first_item=0):
@@ -334,6 +340,7 @@ class WaveletAttribution2D(BaseWAM2D):
                              channels_last=channels_last, _grad=self._grad)
         self._avg_dev = None
         self._scales_res = None
+        self.smooth_mean = None  # S / n of the last 'smooth_sq' / 'vargrad' call
 
     # ------------------------------------------------------------------ .scales
     # The reference recomputes self.scales = reproject_wam(result) at the end of every SmoothGrad /
@@ -429,8 +436,11 @@ class WaveletAttribution2D(BaseWAM2D):
         last = gk[-n:] if gk.dim() == 4 else gk[-n * c:]
         return maps, bmax, last
 
-    def smooth_gradcam(self, x, y):
-        """lib/wam_2D.py:379-415."""
+    def smooth_gradcam(self, x, y, moment=None):
+        """lib/wam_2D.py:379-415. moment (build-only): None = the SmoothGrad mean; 'smooth_sq' /
+        'vargrad' = the mean square / the population variance of the same per-sample mosaic values
+        over the noise samples (wam_frame_moments: the sum S and the sum of squares Q in float64 from
+        one pass over the maps), with the mean S / n of that run left in self.smooth_mean."""
         dev = self._dev
         x = self._prep(x)
         N, c, h, w = x.shape
@@ -449,6 +459,7 @@ class WaveletAttribution2D(BaseWAM2D):
         # parity mode streams the host-generated legacy noise one model group at a time
         wgroup = group if self.noise == "numpy" else self._wam_group(plan, n_ref, c, group, s_hi - s_lo, shard, axis)
         frame = torch.zeros(n * rh * rw, dtype=torch.float64, device=dev)
+        frame_q = None if moment is None else torch.zeros_like(frame)
         handoff = (self._grad.feeds_bf16_nhwc and c in (1, 3) and bool(plan.caps & CAP_BF16_NHWC)
                    and self.bf16_handoff)
         legacy = None
@@ -486,19 +497,31 @@ class WaveletAttribution2D(BaseWAM2D):
                     with phase("all_reduce_max"):
                         shard.all_reduce_max(bmax)  # per-sample maxima over the whole batch (A.6)
                 with phase("accumulate"):
-                    frame_accumulate(cnt, n, gmap, maps, plan.coeff_numel, bmax, plan.nbands, self.normalize_coeffs,
-                                     frame)
+                    if frame_q is None:
+                        frame_accumulate(cnt, n, gmap, maps, plan.coeff_numel, bmax, plan.nbands,
+                                         self.normalize_coeffs, frame)
+                    else:
+                        frame_moments(cnt, n, gmap, maps, plan.coeff_numel, bmax, plan.nbands, self.normalize_coeffs,
+                                      frame, frame_q)
                 last = (plan, flat, None, cnt * n * c, (cnt - 1) * n, n, c)
         if legacy is not None:
             legacy.finish()
         if last is not None:
             self.wam._record_pass(*last, grad_img=last_g)
         with phase("collectives"):
+            # S and Q are both linear in the samples and per-image: reduced / gathered alike
+            sums = [frame] if frame_q is None else [frame, frame_q]
             if axis == "images":
-                frame = shard.all_gather_rows(frame.view(n, rh * rw), N).reshape(-1)
+                sums = [shard.all_gather_rows(f.view(n, rh * rw), N).reshape(-1) for f in sums]
             else:
-                shard.all_reduce_sum(frame)
-        avg = frame.view(N, rh, rw) / self.n_samples
+                for f in sums:
+                    shard.all_reduce_sum(f)
+        avg = sums[0].view(N, rh, rw) / self.n_samples
+        if frame_q is not None:
+            # the mean by the expression "smooth" returns (equal bits for equal seeds); the moment by
+            # wam_moments_finish
+            self.smooth_mean = avg.cpu().numpy()
+            avg = moments_finish(sums[0], sums[1], self.n_samples, moment).view(N, rh, rw)
         self._set_result(avg)
         return avg.cpu().numpy()
 
@@ -574,6 +597,8 @@ class WaveletAttribution2D(BaseWAM2D):
             return self.smooth_gradcam(x, y)
         if self.method == "integratedgrad":
             return self.intergrated_wam(x, y)
+        if self.method in ("smooth_sq", "vargrad"):
+            return self.smooth_gradcam(x, y, moment=self.method)
         return None
 
     # ------------------------------------------------------------------ reprojection

@@ -23,7 +23,8 @@ from .engine import (LegacyNoise, Shard, auto_group, chunks, ig_weights, input_g
                      model_device, param_grad_sum, require_gpu_device, trainable_params)
 from ._lib import check, lib, ptr, stream_of
 from .profiling import phase
-from .plan import CAP_NOISY_WAVEDEC, cube_accumulate, get_plan, item_sigma, noise_add, subband_maps
+from .plan import (CAP_NOISY_WAVEDEC, cube_accumulate, cube_moments, get_plan, item_sigma, moments_finish, noise_add,
+                   subband_maps)
 
 
 class BaseWAM3D:
@@ -258,12 +259,18 @@ class WaveletAttribution3D(BaseWAM3D):
         self.noise = noise
         self.sample_batch = sample_batch
         self.dist = dist
+        self.smooth_mean = None  # the plain mean cube of the last 'smooth_sq' / 'vargrad' call
         self.wam = BaseWAM3D(model, wavelet=wavelet, J=J, mode=mode, device=device, approx_coeffs=approx_coeffs,
                              instance=instance, normalize=normalize, EPS=EPS, frame=frame,
                              autocast_dtype=autocast_dtype)
 
-    def smooth(self, x, y=None, permute=None):
-        """lib/wam_3D.py:550-591 (noise on channel 0 only; legacy in-loop averaging)."""
+    def smooth(self, x, y=None, permute=None, moment=None):
+        """lib/wam_3D.py:550-591 (noise on channel 0 only; legacy in-loop averaging). moment
+        (build-only): 'smooth_sq' / 'vargrad' = the mean square / the population variance of the
+        per-sample |gradient| cubes over the noise samples (wam_cube_moments: sum and sum of squares
+        in float64, one pass over the maps; float32 results). These use the PLAIN mean over the
+        samples, not the reference's in-loop averaging of 'smooth' (weights n^-(n-s)); that plain mean
+        of the same run is left in self.smooth_mean."""
         dev = self._dev
         x = torch.as_tensor(x).detach().to(dev, torch.float32).contiguous()
         S = x.shape[-1]
@@ -282,7 +289,8 @@ class WaveletAttribution3D(BaseWAM3D):
         legacy = None
         if self.noise == "numpy":
             legacy = LegacyNoise(sigma.cpu().numpy(), sp, self.random_seed, self.n_samples, dev)
-        acc = torch.zeros(n * S ** 3, dtype=torch.float32, device=dev)
+        acc = torch.zeros(n * S ** 3, dtype=torch.float32 if moment is None else torch.float64, device=dev)
+        acc_q = None if moment is None else torch.zeros_like(acc)
         ns = self.n_samples
         with param_grad_sum(trainable_params(self.model), shard):
             for s0, cnt in chunks(s_lo, s_hi, group):
@@ -302,7 +310,10 @@ class WaveletAttribution3D(BaseWAM3D):
                         flat = plan.wavedec(noisy.view((cnt * n * c,) + sp))
                 with phase("waverec3+model+adjoint"):
                     cg = self._grads(plan, flat, cnt * n * c, y, cnt, n, c)
-                if shard.world == 1:
+                if moment is not None:
+                    maps, _ = subband_maps(plan, cg, cnt, n, 1, want_max=False)
+                    cube_moments(cnt, n, frames.cube_map(plan, S, dev), maps, plan.coeff_numel, acc, acc_q)
+                elif shard.world == 1:
                     self._cube_from_grads(plan, cg, cnt * n * c, cnt, n, S, acc, 0, n_total=float(ns))
                 else:
                     w = torch.from_numpy(legacy3d_weights(s0, cnt, ns)).to(dev)
@@ -313,6 +324,11 @@ class WaveletAttribution3D(BaseWAM3D):
             legacy.finish()
         with phase("collectives"):
             shard.all_reduce_sum(acc)
+            if acc_q is not None:  # linear in the samples, like the sum
+                shard.all_reduce_sum(acc_q)
+        if moment is not None:
+            self.smooth_mean = moments_finish(acc, acc_q, ns, "mean", torch.float32).view(n, S, S, S).cpu().numpy()
+            acc = moments_finish(acc, acc_q, ns, moment, torch.float32)
         self._cube_dev = acc.view(n, S, S, S)
         out = self._cube_dev.cpu().numpy()
         self.grads = out
@@ -396,3 +412,5 @@ class WaveletAttribution3D(BaseWAM3D):
             return self.smooth(x, y)
         elif self.method == "integratedgrad":
             return self.intergrated_wam(x, y)
+        elif self.method in ("smooth_sq", "vargrad"):
+            return self.smooth(x, y, moment=self.method)

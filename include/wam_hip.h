@@ -382,6 +382,16 @@ int wam_quantize_resize_normalize(int64_t images, int channels, int in_h, int in
  * accumulation order; tmp: items * h * w doubles of scratch. */
 int wam_gaussian_filter2d(int64_t items, int h, int w, const double* weights, int radius, const double* in,
                           double* tmp, double* out, void* stream);
+/* The same filter on items of d x h x w float64 volumes (Eval3DWAM.mu_fidelity): three 1-D passes over
+ * axes 0, 1, 2 of every item with the pass of the 2D entry -- x0 * w[0], then acc + (x[-j] + x[+j]) * w[j]
+ * for j = radius .. 1, every product and sum rounded, no fma -- which is scipy.ndimage.gaussian_filter's
+ * float64 result bit for bit (mode 'reflect', any number of reflections: an extent may be smaller than
+ * the radius). Pass order in -> out, out -> tmp, tmp -> out: `in` is left untouched, tmp and out hold
+ * items * d * h * w doubles each and are distinct from `in` and from each other. radius 0 copies `in`
+ * through the three passes (x * w[0] each). WAM_ERR_INVALID_ARG: items < 0, an extent < 1, d * h * w >
+ * INT32_MAX, radius < 0 or > 64, a NULL weights, in, tmp or out. items == 0 returns WAM_OK. */
+int wam_gaussian_filter3d(int64_t items, int d, int h, int w, const double* weights, int radius,
+                          const double* in, double* tmp, double* out, void* stream);
 /* out[m, p] = grid[m, cell[p]]  (nearest-neighbour zoom through a precomputed cell map) */
 int wam_upsample_masks(int64_t n_masks, int64_t grid_len, const float* grid, int64_t out_len,
                        const int32_t* cell, float* out, void* stream);
@@ -556,6 +566,54 @@ int    wam_waverec1_ranked(const wam_plan* plan, int64_t sets, const float* coef
  * spans of 4096 elements over all rows. rows == 0 returns WAM_OK. */
 int    wam_peak_divide(int64_t rows, int64_t len, const float* in, const float* row_max, float* out,
                        int32_t* silent, int zero_silent, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Cell-mask synthesis: the reconstructions of every volume under n_masks float-valued superpixel masks,
+ * in one call (Eval3DWAM.mu_fidelity; an addition, the reference evaluates no volumes). 3D plans only.
+ * coeffs: band-major coefficients of `sets` volumes as wam_wavedec writes them. slot [K] int32 (device),
+ * K = wam_plan_coeff_numel, shared by all sets: slot[k] = the grid cell of the coefficient at per-item
+ * offset k. grid [sets, n_masks, grid_len] float32 (device): every set has its own masks. Output volume
+ * s * n_masks + m is wam_waverec of set s with every coefficient -- the approximation like any other
+ * band -- multiplied by f = grid[(s * n_masks + m) * grid_len + slot[k]] when 0 <= slot[k] < grid_len and
+ * by f = 1.0f otherwise, so that any slot value is memory-safe. The product is one fp32 multiply c * f,
+ * not a select: a NaN coefficient times 0 stays NaN, a negative one times 0 is -0.0f. The synthesis
+ * after it is wam_waverec's with scale 1.
+ * Routes, as in the ranked section above, bit-identical to each other:
+ *   route 0: the masked sets are written band-major into the workspace (over the 1 + 7 * levels bands)
+ *     and the plan's wam_waverec reads them: every 3D plan, any alignment. Workspace: sets * n_masks * K
+ *     floats rounded up to 16 bytes, followed by wam_plan_workspace_bytes(plan, sets * n_masks);
+ *   route 1: 3D Haar plans with levels <= 2 and dimensions divisible by 2^levels whose wam_waverec runs
+ *     the fused block kernel (not WAM_PLAN_GENERIC). A workgroup serves one set and a chunk of up to 16
+ *     masks: a thread loads its block's coefficients and slots once and, per mask, gathers the factors
+ *     from the mask's grid row, multiplies, inverts the levels and stores the block; no masked coefficient
+ *     is stored and no workspace is read. It takes grid_len <= 65535 (a thread keeps its cells in 16 bits;
+ *     the default 8^3 grid has 512; measured at 64 and 512 cells only), at most 65535 sets, out 16-byte and
+ *     coeffs and slot 8-byte aligned. The gather reads global memory through the caches; staging the rows
+ *     in LDS first measured 3 to 4 % slower at 128^3 and is kept as a build option only (it would bound
+ *     grid_len by 1023);
+ *   route -1: the plan's own route, which wam_waverec_cells_route returns.
+ * Forcing route 1 on a plan, a grid_len or pointers it cannot take returns WAM_ERR_UNSUPPORTED and
+ * launches nothing. With route -1 such a call runs route 0 when a workspace is given and returns
+ * WAM_ERR_UNSUPPORTED without one.
+ * Errors. A plan of another dimension: WAM_ERR_UNSUPPORTED. WAM_ERR_INVALID_ARG: a NULL plan, coeffs,
+ * slot, grid or out, sets < 0, n_masks < 1, grid_len < 1, a host-only plan, another route value, more
+ * than 65535 * 16 masks, and a NULL or misaligned (16 bytes) workspace on route 0; nothing is launched
+ * then. sets == 0 returns WAM_OK.
+ * ---------------------------------------------------------------------------------------------- */
+/* the route a plan takes by itself: 1 = the fused Haar kernel wherever it applies, else 0. Route 1 was the
+ * faster one at every geometry of profiles/eval3d_cells_kbench.txt, its slowest round against route 0's
+ * fastest: Haar J=2 at 128^3 with 1 and 4 volumes x 128 masks on an 8^3 grid (about 0.19 against 0.63 -
+ * 0.67 ms and 0.72 against 2.3 ms), Haar J=1 and J=2 at 16^3 with 16 volumes x 128 masks on a 4^3 grid
+ * (about 11 against 34 us and 13 against 32 us). Works on host-only plans; negative for a NULL plan
+ * (-WAM_ERR_INVALID_ARG) or a plan of another dimension (-WAM_ERR_UNSUPPORTED). */
+int    wam_waverec_cells_route(const wam_plan* plan);
+/* bytes of workspace wam_waverec_cells needs on `route`: route 1 none; route 0 as above; -1 the own
+ * route's size (0 where it is route 1: size it with route 0 when grid_len may exceed route 1's limit).
+ * 0 for invalid arguments. Works on host-only plans. */
+size_t wam_waverec_cells_workspace_bytes(const wam_plan* plan, int64_t sets, int64_t n_masks, int route);
+int    wam_waverec_cells(const wam_plan* plan, int64_t sets, const float* coeffs, const int32_t* slot,
+                         int64_t n_masks, int64_t grid_len, const float* grid, int route /* -1: the plan's own */,
+                         float* out /* [sets * n_masks, *rec_shape] */, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * WAMAnalyzer2D (src/analyzers.py:16-203, src/analyzers_helpers.py:6-134): necessary components

@@ -100,6 +100,7 @@ _SIGS = {
                                               c_int, c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_f32),
                                               ctypes.POINTER(c_f32), c_vp, c_vp, c_vp]),
     "wam_gaussian_filter2d": (c_int, [c_i64, c_int, c_int, c_dp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "wam_gaussian_filter3d": (c_int, [c_i64, c_int, c_int, c_int, c_dp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "wam_upsample_masks": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wam_masked_sums": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wam_rank_mask_coeffs": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
@@ -117,6 +118,9 @@ _SIGS = {
     "wam_waverec1_ranked_workspace_bytes": (ctypes.c_size_t, [c_vp, c_i64, c_i64, c_int]),
     "wam_waverec1_ranked": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp,
                                     c_vp, c_vp]),
+    "wam_waverec_cells_route": (c_int, [c_vp]),
+    "wam_waverec_cells_workspace_bytes": (ctypes.c_size_t, [c_vp, c_i64, c_i64, c_int]),
+    "wam_waverec_cells": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
     "wam_peak_divide": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "wam_threshold_mask_coeffs": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_int,
                                           ctypes.POINTER(ctypes.c_int32), c_int, c_vp, c_vp]),

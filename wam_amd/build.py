@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libwam_hip.so")
 OBJ_CACHE = os.path.join(os.path.dirname(HERE), "build", "obj")
 SOURCES = ["plan.hip", "timing.hip", "dwt_axis.hip", "dwt_adjoint.hip", "dwt2_fused.hip", "dwt2_rows.hip", "dwt2_plane.hip",
-           "dwt1_tile.hip", "dwt3_haar.hip", "dwt3_tile.hip", "epilogue.hip", "evaluate.hip", "evaluate1d.hip", "evaluate_ranked.hip", "analyze2d.hip", "baselines2d.hip", "cam_tiled.hip", "visualize3d.hip", "scalestats.hip", "melspec.hip",
+           "dwt1_tile.hip", "dwt3_haar.hip", "dwt3_tile.hip", "epilogue.hip", "evaluate.hip", "evaluate1d.hip", "evaluate_ranked.hip", "evaluate_cells.hip", "analyze2d.hip", "baselines2d.hip", "cam_tiled.hip", "visualize3d.hip", "scalestats.hip", "melspec.hip",
            "model_ew.hip", "model_pw.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WAM_OFFLOAD_ARCH", "gfx950")

@@ -8,6 +8,7 @@
 // need 3 passes per level with intermediate volumes in HBM; this is one pass over the data.
 // Arithmetic follows the per-axis kernels exactly (W then H then D; fmaf chains starting at 0),
 // so results are bit-identical to the generic path.
+#include "dispatch.hpp"
 #include "maskexpand.hpp"
 #include "rng.hpp"
 
@@ -387,6 +388,164 @@ __global__ void __launch_bounds__(kT3) k_haar3_syn_ranked(const float* __restric
   }
 }
 
+// Cell-mask synthesis (wam_waverec_cells, route 1): k_haar3_syn_ranked with float masks looked up through
+// a coefficient -> grid-cell table instead of a rank threshold. The grid is (blocks of one volume, chunks
+// of masks, sets), so a workgroup serves one set and `chunk` of its mask rows (the launcher's choice, at
+// most kMaskChunk). A thread reads its block's coefficients and slots once -- a slot outside [0, grid_len)
+// becomes column grid_len, which reads as 1.0f -- then for every mask of the chunk multiplies (c * f, one
+// fp32 multiply: NaN * 0 stays NaN), inverts the levels in registers and stores the block. The arithmetic
+// is the expansion's multiply followed by k_haar3_syn's chains with scale 1: bit-identical to route 0.
+// STAGE = false, the default, gathers f from the mask's row in global memory: the rows are small (512
+// floats at the default grid) and stay in the caches. STAGE = true (-DWAM_CELLS_LDS=1, kernels.hpp) stages
+// the chunk's rows in LDS first, grid_len + 1 floats per row whose last is 1.0f, so that the lookup is one
+// LDS read without a compare. The direct form measured 3 to 4 % faster at 128^3, the same at 16^3 J = 1
+// and 6 % slower at 16^3 J = 2 (profiles/eval3d_cells_kbench.txt), and it has no LDS bound on grid_len.
+template <int J, bool STAGE>
+__global__ void __launch_bounds__(kT3) k_haar3_syn_cells(const float* __restrict__ coeffs,
+                                                        const int32_t* __restrict__ slot, int64_t n_masks,
+                                                        int grid_len, const float* __restrict__ grid,
+                                                        float* __restrict__ out, const float* __restrict__ filt,
+                                                        Haar3Geom g, int64_t nb, int chunk) {
+  constexpr int B = 1 << J;
+  constexpr int B1 = B / 2;
+  extern __shared__ float cell_rows[];  // [masks of the chunk][grid_len + 1]
+  const int64_t item = blockIdx.z;
+  const int T = blockDim.x;  // kT3, or the waves that hold a small volume's blocks
+  const int64_t m0 = (int64_t)blockIdx.y * chunk;
+  const int64_t m1 = m0 + chunk < n_masks ? m0 + chunk : n_masks;
+  const int stride = grid_len + 1;
+  const float* grow0 = grid + (item * n_masks + m0) * grid_len;
+  if constexpr (STAGE) {
+    const int nrow = (int)(m1 - m0);
+    for (int r = 0; r < nrow; ++r) {
+      for (int c = threadIdx.x; c < grid_len; c += T) cell_rows[r * stride + c] = grow0[(int64_t)r * grid_len + c];
+      if (threadIdx.x == 0) cell_rows[r * stride + grid_len] = 1.0f;
+    }
+    __syncthreads();
+  }
+  const int64_t t = (int64_t)blockIdx.x * T + threadIdx.x;
+  if (t >= nb) return;
+  const int64_t bw = g.W / B, bh = g.H / B;
+  const int64_t bx = t % bw, by = (t / bw) % bh, bz = t / (bw * bh);
+  const float r[4] = {filt[0], filt[1], filt[2], filt[3]};  // rec lo0 lo1, rec hi0 hi1
+  // a slot outside [0, grid_len) becomes column grid_len; grid_len <= kCellsMaxGrid, so a column fits 16
+  // bits and two share a register (64 slots at J = 2: 32 VGPRs less, which keeps two waves per SIMD)
+  auto col = [&](int32_t s) { return (uint32_t)((uint32_t)s < (uint32_t)grid_len ? s : grid_len); };
+  auto put = [](uint32_t(&w)[4], int k, uint32_t c) { w[k >> 1] |= c << ((k & 1) * 16); };
+  auto get = [](const uint32_t(&w)[4], int k) { return (int)((w[k >> 1] >> ((k & 1) * 16)) & 0xffffu); };
+  const int64_t d1 = g.D / 2, h1 = g.H / 2, w1 = g.W / 2;
+  const int64_t n1 = d1 * h1 * w1;
+  float c2[8];
+  uint32_t s2[4] = {0, 0, 0, 0};
+  float c1[B1][B1][B1][8];
+  uint32_t s1[B1][B1][B1][4];
+#pragma unroll
+  for (int z = 0; z < B1; ++z)
+#pragma unroll
+    for (int y = 0; y < B1; ++y)
+#pragma unroll
+      for (int x = 0; x < B1; ++x)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s1[z][y][x][q] = 0;
+  if constexpr (J == 1) {
+    const int64_t o = (bz * h1 + by) * w1 + bx;
+    c1[0][0][0][0] = coeffs[g.items * g.off_a + item * n1 + o];
+    put(s1[0][0][0], 0, col(slot[g.off_a + o]));
+  } else {
+    const int64_t h2 = h1 / 2, w2 = w1 / 2, n2 = (d1 / 2) * h2 * w2, o = (bz * h2 + by) * w2 + bx;
+    c2[0] = coeffs[g.items * g.off_a + item * n2 + o];
+    put(s2, 0, col(slot[g.off_a + o]));
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+      c2[k] = coeffs[g.items * g.off[1][k - 1] + item * n2 + o];
+      put(s2, k, col(slot[g.off[1][k - 1] + o]));
+    }
+  }
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    const float* src = coeffs + g.items * g.off[0][k - 1] + item * n1;
+    const int32_t* ss = slot + g.off[0][k - 1];
+#pragma unroll
+    for (int z = 0; z < B1; ++z)
+#pragma unroll
+      for (int y = 0; y < B1; ++y) {
+        const int64_t o = ((bz * B1 + z) * h1 + (by * B1 + y)) * w1 + bx * B1;
+        if constexpr (B1 == 2) {
+          const float2 q = *reinterpret_cast<const float2*>(src + o);
+          const int2 sq = *reinterpret_cast<const int2*>(ss + o);
+          c1[z][y][0][k] = q.x;
+          c1[z][y][1][k] = q.y;
+          put(s1[z][y][0], k, col(sq.x));
+          put(s1[z][y][1], k, col(sq.y));
+        } else {
+          c1[z][y][0][k] = src[o];
+          put(s1[z][y][0], k, col(ss[o]));
+        }
+      }
+  }
+  const int64_t vol = g.D * g.H * g.W;
+  float* dst0 = out + item * n_masks * vol + (bz * B * g.H + by * B) * g.W + bx * B;
+#pragma unroll 1
+  for (int64_t m = m0; m < m1; ++m) {
+    // the packed columns are unpacked per mask: without this the unpacking is hoisted out of the loop and
+    // the 64 columns of J = 2 take a register each again (262 VGPRs, one wave per SIMD)
+    if constexpr (J == 2) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(s2[q]));
+    }
+#pragma unroll
+    for (int z = 0; z < B1; ++z)
+#pragma unroll
+      for (int y = 0; y < B1; ++y)
+#pragma unroll
+        for (int x = 0; x < B1; ++x)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(s1[z][y][x][q]));
+    const float* lrow = cell_rows + (int)(m - m0) * stride;
+    const float* grow = grow0 + (m - m0) * grid_len;
+    auto f = [&](int s) {
+      if constexpr (STAGE) return lrow[s];
+      else return s < grid_len ? grow[s] : 1.0f;
+    };
+    float ll[B1][B1][B1];
+    if constexpr (J == 1) {
+      ll[0][0][0] = c1[0][0][0][0] * f(get(s1[0][0][0], 0));
+    } else {
+      float cm[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cm[k] = c2[k] * f(get(s2, k));
+      haar3_inv(cm, r, ll);
+    }
+    float* dst = dst0 + m * vol;
+#pragma unroll
+    for (int z = 0; z < B1; ++z)
+#pragma unroll
+      for (int y = 0; y < B1; ++y) {
+        float v[2][2][B];  // rows (2z + a, 2y + b) of the block
+#pragma unroll
+        for (int x = 0; x < B1; ++x) {
+          float cm[8], blk[2][2][2];
+          cm[0] = ll[z][y][x];
+#pragma unroll
+          for (int k = 1; k < 8; ++k) cm[k] = c1[z][y][x][k] * f(get(s1[z][y][x], k));
+          haar3_inv(cm, r, blk);
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) v[a][b][2 * x] = blk[a][b][0], v[a][b][2 * x + 1] = blk[a][b][1];
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            float* row = dst + ((int64_t)(2 * z + a) * g.H + (2 * y + b)) * g.W;
+            if constexpr (B == 4) wam_st4(row, v[a][b][0], v[a][b][1], v[a][b][2], v[a][b][3]);
+            else wam_st(reinterpret_cast<wam_f2v*>(row), wam_f2v{v[a][b][0], v[a][b][1]});
+          }
+      }
+  }
+}
+
 Haar3Geom make_geom3(const wam_plan* p, int64_t items) {
   Haar3Geom g{};
   g.J = p->levels;
@@ -501,6 +660,51 @@ int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const flo
   else
     hipLaunchKernelGGL(k_haar3_syn_ranked<2>, gd, dim3(kT3), 0, st, coeffs, rank, rank_len, pos, out, filt, g, blocks,
                        n_iter, n_comp, deletion);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
+}
+
+// The fused route of wam_waverec_cells. Declines (WAM_ERR_UNSUPPORTED) what the kernel cannot take: out
+// not 16-byte, coeffs or slot not 8-byte aligned, a grid_len above kCellsMaxGrid (its 16-bit columns),
+// more sets than gridDim.z holds.
+int launch_dwt3_haar_synthesis_cells(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* slot,
+                                     int64_t n_masks, int64_t grid_len, const float* grid, float* out,
+                                     hipStream_t st) {
+  if (!dwt3_haar_supported(p) || !aligned16(out) || ((uintptr_t)coeffs & 7) || ((uintptr_t)slot & 7) ||
+      grid_len > kCellsMaxGrid || sets > 65535)
+    return WAM_ERR_UNSUPPORTED;
+  const Haar3Geom g = make_geom3(p, sets);
+  const int B = 1 << p->levels;
+  const int64_t nb = (g.D / B) * (g.H / B) * (g.W / B);
+  // A volume of fewer than kT3 blocks takes the waves that hold them. A thread keeps its coefficients for
+  // a chunk of kMaskChunk masks; where that leaves the chip short of work (16^3 at J = 2: 64 blocks per
+  // volume, one wave per set and chunk) the chunk is halved until the grid holds two waves per SIMD, the
+  // residency of the J = 2 kernel, or a mask per workgroup: the coefficients are re-read from L2.
+  const int threads = nb < kT3 ? (int)((nb + 63) / 64 * 64) : kT3;
+  const int64_t gx = (nb + threads - 1) / threads;
+  if (gx > 0x7fffffff) return WAM_ERR_UNSUPPORTED;
+  if ((n_masks + kMaskChunk - 1) / kMaskChunk > 65535) return WAM_ERR_INVALID_ARG;
+  int cus = 0;
+  WAM_HIP_CHECK(wam_device_cus(&cus));
+  int chunk = kMaskChunk;
+  while (chunk > 1 && gx * (threads / 64) * ((n_masks + chunk - 1) / chunk) * sets < 8 * (int64_t)cus &&
+         (n_masks + chunk / 2 - 1) / (chunk / 2) <= 65535)
+    chunk /= 2;
+  const int64_t chunks = (n_masks + chunk - 1) / chunk;
+  const float* filt = p->d_filt + WAM_F_SYN_LO * p->L;  // rec lo0 lo1 hi0 hi1
+  const double K = (double)p->band_off[p->nbands];
+  constexpr bool kStage = WAM_CELLS_LDS != 0;
+  const int64_t rows = n_masks < chunk ? n_masks : chunk;
+  const size_t lds = kStage ? (size_t)(rows * (grid_len + 1)) * sizeof(float) : 0;
+  WamTimer tm(st, "k_haar3_syn_cells",
+              4.0 * (sets * K + K + (double)sets * n_masks * grid_len + (double)sets * n_masks * g.D * g.H * g.W));
+  const dim3 gd((unsigned)gx, (unsigned)chunks, (unsigned)sets);
+  if (p->levels == 1)
+    hipLaunchKernelGGL((k_haar3_syn_cells<1, kStage>), gd, dim3(threads), lds, st, coeffs, slot, n_masks,
+                       (int)grid_len, grid, out, filt, g, nb, chunk);
+  else
+    hipLaunchKernelGGL((k_haar3_syn_cells<2, kStage>), gd, dim3(threads), lds, st, coeffs, slot, n_masks,
+                       (int)grid_len, grid, out, filt, g, nb, chunk);
   WAM_LAUNCH_CHECK();
   return WAM_OK;
 }

@@ -127,28 +127,44 @@ struct GaussW {
   double w[kMaxGaussR + 1];  // w[j] = weight at offset +-j
 };
 
-template <int AXIS>
-__global__ void __launch_bounds__(256) k_gauss_pass(int64_t items, int h, int w, int radius, GaussW gw,
+// One pass along an axis of length n whose elements lie `inner` apart, over `outer` slabs of n * inner
+// doubles: (items, h, w) for axis 0 of a plane, (items * h, w, 1) for its axis 1, and likewise the three
+// axes of a volume. UNIT: inner == 1, no division by it.
+template <bool UNIT>
+__global__ void __launch_bounds__(256) k_gauss_pass(int64_t outer, int n, int inner, int radius, GaussW gw,
                                                     const double* __restrict__ in, double* __restrict__ out) {
   // hipcc contracts a multiply into a following add by default, also through __dmul_rn / __dadd_rn (inline
   // functions of the headers, outside this pragma's reach): plain operators under contract(off) keep the
   // product and the sum rounded separately, which is what holds the result to scipy's bits
 #pragma clang fp contract(off)
-  const int64_t plane = (int64_t)h * w;
-  const int64_t total = items * plane;
+  const int64_t slab = (int64_t)n * inner;  // <= INT32_MAX (host check)
+  const int64_t total = outer * slab;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t it = t / plane;
-    const int p = (int)(t - it * plane);
-    const int r = p / w, c = p - r * w;
-    const double* x = in + it * plane;
+    const int64_t o = t / slab;
+    const int p = (int)(t - o * slab);
+    const int i = UNIT ? p : p / inner, k = UNIT ? 0 : p - i * inner;
+    const double* x = in + o * slab + k;
     auto at = [&](int d) -> double {
-      if (AXIS == 0) return x[(int64_t)wam_ext_index(r + d, h, WAM_MODE_SYMMETRIC) * w + c];
-      return x[(int64_t)r * w + wam_ext_index(c + d, w, WAM_MODE_SYMMETRIC)];
+      return x[(int64_t)wam_ext_index(i + d, n, WAM_MODE_SYMMETRIC) * (UNIT ? 1 : inner)];
     };
     double acc = at(0) * gw.w[0];
     for (int j = radius; j >= 1; --j) acc = acc + (at(-j) + at(j)) * gw.w[j];
     out[t] = acc;
   }
+}
+
+int launch_gauss_pass(int64_t outer, int n, int64_t inner, int radius, const GaussW& gw, const double* in, double* out,
+                      hipStream_t st) {
+  const int64_t work = outer * n * inner;
+  WamTimer tm(st, "k_gauss_pass", 16.0 * work);
+  if (inner == 1)
+    hipLaunchKernelGGL(k_gauss_pass<true>, dim3(wam_grid(work, 256)), dim3(256), 0, st, outer, n, 1, radius, gw, in,
+                       out);
+  else
+    hipLaunchKernelGGL(k_gauss_pass<false>, dim3(wam_grid(work, 256)), dim3(256), 0, st, outer, n, (int)inner, radius,
+                       gw, in, out);
+  WAM_LAUNCH_CHECK();
+  return WAM_OK;
 }
 
 // ---- nearest-neighbour upsampling of grid masks through a precomputed cell map (scipy zoom,
@@ -267,15 +283,22 @@ int wam_gaussian_filter2d(int64_t items, int h, int w, const double* weights, in
   GaussW gw{};
   for (int j = 0; j <= radius; ++j) gw.w[j] = weights[j];
   hipStream_t st = (hipStream_t)stream;
-  {
-    WamTimer tm(st, "k_gauss_pass", 16.0 * work);
-    hipLaunchKernelGGL(k_gauss_pass<0>, dim3(wam_grid(work, 256)), dim3(256), 0, st, items, h, w, radius, gw, in, tmp);
-    WAM_LAUNCH_CHECK();
-  }
-  WamTimer tm(st, "k_gauss_pass", 16.0 * work);
-  hipLaunchKernelGGL(k_gauss_pass<1>, dim3(wam_grid(work, 256)), dim3(256), 0, st, items, h, w, radius, gw, tmp, out);
-  WAM_LAUNCH_CHECK();
-  return WAM_OK;
+  if (int rc = launch_gauss_pass(items, h, w, radius, gw, in, tmp, st)) return rc;
+  return launch_gauss_pass(items * h, w, 1, radius, gw, tmp, out, st);
+}
+
+int wam_gaussian_filter3d(int64_t items, int d, int h, int w, const double* weights, int radius, const double* in,
+                          double* tmp, double* out, void* stream) {
+  if (items < 0 || d < 1 || h < 1 || w < 1 || (int64_t)d * h * w > INT32_MAX || radius < 0 || radius > kMaxGaussR ||
+      !weights || !in || !tmp || !out)
+    return WAM_ERR_INVALID_ARG;
+  if (items == 0) return WAM_OK;
+  GaussW gw{};
+  for (int j = 0; j <= radius; ++j) gw.w[j] = weights[j];
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch_gauss_pass(items, d, (int64_t)h * w, radius, gw, in, out, st)) return rc;
+  if (int rc = launch_gauss_pass(items * d, h, w, radius, gw, out, tmp, st)) return rc;
+  return launch_gauss_pass(items * d * h, w, 1, radius, gw, tmp, out, st);
 }
 
 int wam_upsample_masks(int64_t n_masks, int64_t grid_len, const float* grid, int64_t out_len, const int32_t* cell,

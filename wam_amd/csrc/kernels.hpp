@@ -194,6 +194,20 @@ int launch_dwt3_haar_synthesis(const wam_plan* p, int64_t batch, const float* co
 int launch_dwt3_haar_synthesis_ranked(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* rank,
                                       int64_t rank_len, const int32_t* pos, int64_t n_iter, int64_t n_comp,
                                       int deletion, float* out, hipStream_t st);
+// The fused route of wam_waverec_cells (evaluate_cells.hip; dwt3_haar.hip): out = sets * n_masks volumes,
+// every coefficient times its grid cell's value of the mask, read through slot. Declines
+// (WAM_ERR_UNSUPPORTED, nothing launched) a plan, a grid_len above kCellsMaxGrid, more than 65535 sets or
+// pointers its kernel cannot take. The kernel has two forms: the mask rows gathered straight from global
+// memory (the default: 3 to 4 % faster at 128^3, profiles/eval3d_cells_kbench.txt), or staged in LDS per
+// workgroup first (-DWAM_CELLS_LDS=1, kept for A/B runs).
+#ifndef WAM_CELLS_LDS
+#define WAM_CELLS_LDS 0
+#endif
+// a thread keeps its columns of the mask rows in 16 bits; staged, kMaskChunk rows of grid_len + 1 floats fill 64 KiB of LDS
+constexpr int64_t kCellsMaxGrid = WAM_CELLS_LDS ? 1023 : 65535;
+int launch_dwt3_haar_synthesis_cells(const wam_plan* p, int64_t sets, const float* coeffs, const int32_t* slot,
+                                     int64_t n_masks, int64_t grid_len, const float* grid, float* out,
+                                     hipStream_t st);
 // 1D (dwt1_tile.hip): k_dwt1_syn_int with the threshold applied as a unit's coefficients are staged.
 // out [sets * (n_iter + 1), rec_len]; row_max (may be NULL) must hold -inf.
 bool dwt1_syn_ranked_supported(const wam_plan* p);

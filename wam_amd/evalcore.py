@@ -121,6 +121,31 @@ def zoom_cell_map(grid, hw):
     return zoom(idx, (1, hw[0] / grid, hw[1] / grid), order=0)[0].astype(np.int64)
 
 
+def zoom_cell_map3(grid, S):
+    """scipy.ndimage.zoom(masks, (1, S / grid, S / grid, S / grid), order=0) of [n, grid, grid, grid] masks
+    as a per-voxel grid-cell index map, int64 [S, S, S] (cells in C order): the zoom of the cell-index
+    volume, nearest neighbour copies values exactly. ValueError unless the result is (S, S, S) and every
+    cell holds a voxel."""
+    grid, S = int(grid), int(S)
+    if grid < 1 or S < 1:
+        raise ValueError("zoom_cell_map3: grid_size %d and volume size %d must be positive" % (grid, S))
+    idx = np.arange(grid ** 3, dtype=np.float64).reshape(grid, grid, grid)
+    cell = np.rint(zoom(idx, (S / grid,) * 3, order=0)).astype(np.int64)
+    if cell.shape != (S, S, S) or np.unique(cell).size != grid ** 3:
+        raise ValueError("a %d^3 superpixel grid does not cover a %d^3 volume with every cell non-empty "
+                         "(zoomed to %s, %d of %d cells used)" % (grid, S, cell.shape, np.unique(cell).size, grid ** 3))
+    return cell
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """scipy's _gaussian_kernel1d(sigma, 0, int(truncate * sigma + 0.5)): w[j] for |offset| j."""
+    r = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return phi[r:], r
+
+
 def device_table(key, make):
     """make() -- a host-built table moved to the device -- once per key (the key names the device)."""
     if key not in _TABLES:
@@ -142,9 +167,16 @@ def cell_map(grid_size, hw, dev):
         zoom_cell_map(grid_size, hw).astype(np.int32)).to(dev).reshape(-1))
 
 
+def cell_map3(grid_size, S, dev):
+    """zoom_cell_map3 as flat int32 [S^3] on `dev`, cached."""
+    return device_table(("cells3", int(grid_size), int(S), dev), lambda: torch.as_tensor(
+        zoom_cell_map3(grid_size, S).astype(np.int32)).to(dev).reshape(-1))
+
+
 def masked_sums(values, subsets, cell):
     """wam_masked_sums (sum_importance, src/evaluation_helpers.py:361-393): values float64 [H * W] on the
-    device, subsets [n, grid, grid] float32 (host), cell from cell_map -> per subset the float64 sum of
+    device (or [S^3] of a volume), subsets [n, grid, grid] (or [n, grid, grid, grid]) float32 (host), cell
+    from cell_map (cell_map3) -> per subset the float64 sum of
     the values under its upsampled mask, numpy [n]."""
     dev = values.device
     subd = torch.as_tensor(subsets).to(dev)

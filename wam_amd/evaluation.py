@@ -56,24 +56,14 @@ from .baselines import EvalImageBaselines  # noqa: F401  (the reference keeps it
 from .baselines_audio import EvalAudioBaselines  # noqa: F401  (likewise)
 from .evalcore import (IMAGENET_MEAN, IMAGENET_STD, array_layout, cell_map, check_tie_order,  # noqa: F401
                        class_curves, class_probs, coeff_array_layout, compute_auc, db_melspec, descending_ranks,
-                       device_table, generate_subsets, masked_sums, norm_consts, pil_bilinear_coeffs, rank_mask_rows,
-                       resize_default, show_images, softmax, zoom_cell_map)
+                       device_table, gaussian_weights, generate_subsets, masked_sums, norm_consts,
+                       pil_bilinear_coeffs, rank_mask_rows, resize_default, show_images, softmax, zoom_cell_map)
 from .evaluation3d import Eval3DWAM  # noqa: F401  (the volume evaluator, an addition: its own module)
 from .frames import wam_cell_source
 from .plan import get_plan, peak_divide
 from .wam_1D import WaveletAttribution1D
 from .wam_1D import _peak_normalise as _peak_normalise_1d
 from .wam_2D import WaveletAttribution2D
-
-
-# ------------------------------------------------------------------------------ host geometry
-def gaussian_weights(sigma, truncate=4.0):
-    """scipy's _gaussian_kernel1d(sigma, 0, int(truncate * sigma + 0.5)): w[j] for |offset| j."""
-    r = int(truncate * float(sigma) + 0.5)
-    x = np.arange(-r, r + 1)
-    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
-    phi = phi / phi.sum()
-    return phi[r:], r
 
 
 class Eval2DWAM(WaveletAttribution2D):

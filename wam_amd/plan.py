@@ -162,6 +162,43 @@ class Plan:
         return self._waverec_ranked("wam_waverec_ranked", "ranked", (sets,), flat, rank, pos, n_iter, n_comp,
                                     deletion, route, out)[0]
 
+    # ---- cell-mask synthesis (evaluate_cells.hip)
+    @property
+    def cells_route(self):
+        """The route waverec_cells takes by itself (wam_waverec_cells_route): 0 = mask expansion +
+        waverec, 1 = the fused 3D Haar kernel. 3D plans only."""
+        return self._ranked_route("wam_waverec_cells")
+
+    def waverec_cells(self, flat, sets, slot, grid, route=-1, out=None):
+        """The reconstructions of each of `sets` volumes under its own n_masks float masks
+        (wam_waverec_cells): flat band-major coefficients of the sets, slot int32 [coeff_numel] (the grid
+        cell of every coefficient; outside [0, grid_len): the coefficient is left as it is) and grid
+        float32 [sets, n_masks, grid_len] -> [sets * n_masks, *rec_shape], volume s * n_masks + m.
+        route: -1 the plan's own, 0 expansion + waverec (workspace from the plan), 1 the fused kernel."""
+        require_cuda(flat, "coefficients")
+        require_cuda(grid, "grid")
+        flat, slot, grid = flat.contiguous(), slot.contiguous(), grid.contiguous()
+        if slot.dtype != torch.int32:
+            raise TypeError("wam_amd: slot must be int32")
+        if (flat.numel() != sets * self.coeff_numel or slot.numel() != self.coeff_numel or grid.dim() != 3
+                or grid.shape[0] != sets):
+            raise ValueError("expected %d x %d coefficients, %d slots and %d sets of masks"
+                             % (sets, self.coeff_numel, self.coeff_numel, sets))
+        n_masks, grid_len = int(grid.shape[1]), int(grid.shape[2])
+        if out is None:
+            out = torch.empty((sets * n_masks,) + self.rec_shape, dtype=torch.float32, device=flat.device)
+        # the plan's own route falls back to route 0 above the fused kernel's largest grid: size for it
+        sized = 0 if route < 0 and grid_len > CELLS_FUSED_MAX_GRID else route
+        ws = None
+        n = int(lib.wam_waverec_cells_workspace_bytes(self._h, sets, n_masks, sized))
+        if n:
+            ws = self._ws.get("cells")
+            if ws is None or ws.numel() < n:
+                ws = self._ws["cells"] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(lib.wam_waverec_cells(self._h, sets, ptr(flat), ptr(slot), n_masks, grid_len, ptr(grid), route, ptr(out),
+                                    ptr(ws), stream_of(flat.device)))
+        return out
+
     def ranked2_route(self):
         """The route waverec2_ranked takes by itself (wam_waverec2_ranked_route): 0 = mask expansion +
         waverec, 1 = the fused plane-resident kernel. 2D plans only."""
@@ -313,6 +350,7 @@ PLAN_FORCE_COOP = 16
 CAP_NOISY_WAVEDEC = 1
 CAP_ADJOINT_MAPS = 2
 CAP_BF16_NHWC = 4
+CELLS_FUSED_MAX_GRID = 65535  # the largest grid_len route 1 of wam_waverec_cells takes (include/wam_hip.h)
 
 
 def timing_enable(on=True):
@@ -507,6 +545,23 @@ def moments_finish(sum_, sumsq, n, kind, dtype=torch.float64):
     o64, o32 = (out, None) if dtype == torch.float64 else (None, out)
     check(lib.wam_moments_finish(sum_.numel(), ptr(sum_), ptr(sumsq), int(n), MOMENT_KINDS[kind], ptr(o64), ptr(o32),
                                  stream_of(sum_.device)))
+    return out
+
+
+def gaussian_filter3d(x, weights, radius):
+    """scipy.ndimage.gaussian_filter (mode 'reflect') of float64 volumes on the device
+    (wam_gaussian_filter3d): x [items, d, h, w] or [d, h, w] float64, weights[0 .. radius] the symmetric
+    1-D kernel on the host (evalcore.gaussian_weights) -> a new tensor of x's shape; x is left untouched."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.float64 or x.dim() not in (3, 4):
+        raise TypeError("wam_amd: gaussian_filter3d takes a float64 CUDA (HIP) tensor [items, d, h, w] or [d, h, w]")
+    x = x.contiguous()
+    d, h, w = (int(v) for v in x.shape[-3:])
+    wts = np.ascontiguousarray(weights, dtype=np.float64)
+    if wts.size < radius + 1:
+        raise ValueError("gaussian_filter3d: %d weights for radius %d" % (wts.size, radius))
+    tmp, out = torch.empty_like(x), torch.empty_like(x)
+    check(lib.wam_gaussian_filter3d(x.numel() // (d * h * w), d, h, w, wts.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                    int(radius), ptr(x), ptr(tmp), ptr(out), stream_of(x.device)))
     return out
 
 
